@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Headline benchmark: TRs/sec of the trimodal fMRI encode (SegmentData -> [B, 1000, T']) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, optionally writes the last step's predictions (`--dump-outputs`) and prints
+the headline line.  `--full` adds what the headline does not need: the per-operator roofline (a second, instrumented pass of
+the same K steps), the R = 1 and BASELINE config-1 side points and the CPU baseline.
 
 `python bench.py --gpus N` invoked plainly starts N fresh rank processes itself (one per GPU, the layout of the
 reference's only multi-GPU path, main.py:388-395: one task per GPU): the parent touches no GPU API, picks a free
@@ -46,8 +50,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=16, help="R: stacked passes of the 4-subject batch per rank (B = 4R); R = 4 / 8 / 16 measured 536 k / 548 k / 554 k TRs/s")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-r1-point", action="store_true", help="skip the untimed-headline R = 1 (B = 4) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline / per-operator table, the R = 1 and config-1 side points and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's predictions (rank 0; float32 .npy, fixed seeded sample) into DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-r1-point", action="store_true", help="--full: skip the untimed-headline R = 1 (B = 4) and config-1 measurements")
     ap.add_argument("--exchange", choices=("gather", "stats", "none"), default="gather",
                     help="N > 1: what the ranks exchange per step (bf16 prediction all-gather / f64 Pearson statistics all-reduce / nothing)")
     ap.add_argument("--no-gather", action="store_true", help="same as --exchange none")
@@ -61,6 +69,8 @@ def parse_args(argv=None) -> argparse.Namespace:
         args.exchange = "none"
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -210,6 +220,27 @@ def _role_table(prof: dict) -> dict:
     return table
 
 
+DUMP_SAMPLE = 1 << 22   # f32 values in predictions_sample.npy (16 MiB)
+
+
+def dump_outputs(pred, out_dir: Path) -> None:
+    """`--dump-outputs`: the predictions [B, V, T] of the last timed step, as float32 .npy files (32 MiB at most):
+    predictions_first4.npy  sequences 0..3 whole (one per subject), [min(B, 4), V, T]
+    predictions_sample.npy  DUMP_SAMPLE positions of the whole flattened tensor, drawn once by numpy's default_rng(0) without
+                            replacement and sorted (everything, in order, when the tensor is smaller)"""
+    import numpy as np
+    import torch
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    pred = pred.detach()
+    flat = pred.reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(out_dir / "predictions_first4.npy", pred[:4].float().cpu().numpy())
+    np.save(out_dir / "predictions_sample.npy", flat.float().cpu().numpy())
+
+
 def rehearse_launcher(args, rank: int, world: int) -> None:
     """Stand-in rank body for the CPU test of the N > 1 plumbing: rendezvous, the bf16 exchange, barrier / MAX-over-ranks
     timing and the one JSON line, with host tensors filled with the rank id instead of predictions.  Nothing here is the
@@ -317,18 +348,33 @@ def run_rank(args) -> None:
     pending.clear()
     barrier()
 
-    ops.prof_begin(max_records=(args.steps + 1) * 128)
     start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     start.record()
     for i in range(args.steps):
-        step(i, pending)
+        pred = step(i, pending)
     for w in pending:
         w.wait()
+    pending.clear()
     stop.record()
     barrier()
     elapsed = time.perf_counter() - t0
-    prof = ops.prof_end()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pred, Path(args.dump_outputs))
+    del pred
+
+    prof = None
+    if args.full:
+        # per-operator table: the same steps again with the per-launch HIP event pairs on (they cost a step a few per cent, so the
+        # headline above is timed without them)
+        ops.prof_begin(max_records=(args.steps + 1) * 128)
+        for i in range(args.steps):
+            step(i, pending)
+        for w in pending:
+            w.wait()
+        barrier()
+        prof = ops.prof_end()
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
@@ -343,32 +389,6 @@ def run_rank(args) -> None:
 
     if rank == 0:
         fl = flops_per_tr()
-        # dominant kernel = the operator (GEMM role or the fused attention) with the largest summed time inside the timed region
-        by_kernel = _role_table(prof)
-        dom = max(prof, key=lambda k: prof[k]["ms"])
-        gemm_ms = sum(r["ms"] for r in prof.values()) / args.steps
-        # kernel symbol behind the dominant role at this batch: every GEMM role runs the 8-wave 256 x 256 kernel by default (csrc/gemm.hip:
-        # gemm_plan; the one-wave-per-SIMD gemm_nt_4w256 is tile_hint 5) -- rocprof shows it as gemm_nt_256x256x64<out_bf16, role, 0, 4>
-        dom_name = "attn_fwd_wide384_kernel" if dom == "attention" else f"gemm_nt_256x256x64<{dom}>"
-        roofline = {"bound": "mfma", "kernel": dom_name, "achieved": by_kernel[dom]["achieved_tflops"],
-                    "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": by_kernel[dom]["frac"], "traffic": None,
-                    "traffic_source": None,
-                    "avg_launch_ms": by_kernel[dom]["avg_ms"], "flops_per_launch": by_kernel[dom]["gflop_per_launch"] * 1e9,
-                    "by_kernel": by_kernel,
-                    "whole_path": {"tflops": round(trs / world * fl["total"] / elapsed / 1e12, 1),
-                                   "frac": round(trs / world * fl["total"] / elapsed / 1e12 / PEAK_BF16_TFLOPS, 4),
-                                   "gemm_ms_per_step": round(gemm_ms, 3)}}
-        traffic_file = ROOT / "profiles" / "roofline_traffic.json"
-        if traffic_file.exists():
-            try:
-                measured = json.loads(traffic_file.read_text())
-                if measured.get("_sequences_per_gpu") == B:   # PMC bytes per launch are only comparable at the batch they were taken at
-                    roofline["traffic"] = measured.get(dom)
-                    roofline["traffic_source"] = ("stored: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, gfx950-corrected, "
-                                                  f"committed as profiles/roofline_traffic.json ({measured.get('_source', 'see profiles/')}); "
-                                                  "NOT re-measured in this run")
-            except Exception:
-                pass
         xch = {"gather": f"; bf16 all-gather of predictions over {'RCCL' if args.backend == 'nccl' else args.backend}",
                "stats": f"; f64 Pearson-statistics all-reduce over {'RCCL' if args.backend == 'nccl' else args.backend}",
                "none": ""}[exchange]
@@ -382,12 +402,14 @@ def run_rank(args) -> None:
                        "global_batch": world * B, "seq_len": T, "parallelism": f"dp{world}", "backend": args.backend if world > 1 else None,
                        "flops_per_tr": fl["total"]},
             "gpu_event_ms_per_step": round(start.elapsed_time(stop) / args.steps, 3),
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_r1_point:
+        if prof is not None:
+            out["roofline"] = roofline_of(prof, trs, world, elapsed, args.steps, B)
+            out["roofline"]["by_kernel_source"] = "second, instrumented pass of the timed steps (the headline is timed without the per-launch events)"
+        if args.full and world == 1 and not args.no_r1_point:
             out["r1_point"] = r1_point(model, fdims, device, ops)
             out["config1_point"] = config1_point(device, ops)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del model, batch
             torch.cuda.empty_cache()
             # a 1-GPU box grants 16 CPUs; more threads than that only oversubscribes the share
@@ -396,6 +418,39 @@ def run_rank(args) -> None:
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def roofline_of(prof: dict, trs: int, world: int, elapsed: float, steps: int, B: int) -> dict:
+    """--full: the dominant operator of the instrumented pass against the bf16 MFMA peak, the per-operator table and the
+    whole-path rate of the (clean) timed steps."""
+    fl = flops_per_tr()
+    # dominant kernel = the operator (GEMM role or the fused attention) with the largest summed time in the instrumented pass
+    by_kernel = _role_table(prof)
+    dom = max(prof, key=lambda k: prof[k]["ms"])
+    gemm_ms = sum(r["ms"] for r in prof.values()) / steps
+    # kernel symbol behind the dominant role at this batch: every GEMM role runs the 8-wave 256 x 256 kernel by default (csrc/gemm.hip:
+    # gemm_plan; the one-wave-per-SIMD gemm_nt_4w256 is tile_hint 5) -- rocprof shows it as gemm_nt_256x256x64<out_bf16, role, 0, 4>
+    dom_name = "attn_fwd_wide384_kernel" if dom == "attention" else f"gemm_nt_256x256x64<{dom}>"
+    roofline = {"bound": "mfma", "kernel": dom_name, "achieved": by_kernel[dom]["achieved_tflops"],
+                "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": by_kernel[dom]["frac"], "traffic": None,
+                "traffic_source": None,
+                "avg_launch_ms": by_kernel[dom]["avg_ms"], "flops_per_launch": by_kernel[dom]["gflop_per_launch"] * 1e9,
+                "by_kernel": by_kernel,
+                "whole_path": {"tflops": round(trs / world * fl["total"] / elapsed / 1e12, 1),
+                               "frac": round(trs / world * fl["total"] / elapsed / 1e12 / PEAK_BF16_TFLOPS, 4),
+                               "gemm_ms_per_step": round(gemm_ms, 3)}}
+    traffic_file = ROOT / "profiles" / "roofline_traffic.json"
+    if traffic_file.exists():
+        try:
+            measured = json.loads(traffic_file.read_text())
+            if measured.get("_sequences_per_gpu") == B:   # PMC bytes per launch are only comparable at the batch they were taken at
+                roofline["traffic"] = measured.get(dom)
+                roofline["traffic_source"] = ("stored: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, gfx950-corrected, "
+                                              f"committed as profiles/roofline_traffic.json ({measured.get('_source', 'see profiles/')}); "
+                                              "NOT re-measured in this run")
+        except Exception:
+            pass
+    return roofline
 
 
 def _side_point(model, batch, ops, steps: int, warmup: int):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collects the evidence the bench line is judged against, on the GPU box:  bash scripts/profile_round.sh <tag>   (e.g. r02_f)
-#   <tag>_bench.json                  the default bench.py line (roofline + cpu_baseline + r1_point)
+#   <tag>_bench.json                  the bench.py --full line (roofline + cpu_baseline + r1_point)
 #   <tag>_bench_kernel_stats.{csv,txt} rocprofv3 --kernel-trace --stats of the same command (fewer steps)
 #   <tag>_pmc_traffic.txt              FETCH_SIZE / WRITE_SIZE per GEMM role (separate --pmc passes, gfx950-corrected) -> profiles/roofline_traffic.json
 #   <tag>_mfma_util.json               SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x kernel cycles) per kernel
@@ -11,7 +11,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT" || exit 1
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT" profiles
-python3 bench.py --steps 10 --warmup 3 > profiles/${TAG}_bench.json 2> "$OUT/bench.err" || { echo "bench failed"; tail -5 "$OUT/bench.err"; exit 1; }
+python3 bench.py --full --steps 10 --warmup 3 > profiles/${TAG}_bench.json 2> "$OUT/bench.err" || { echo "bench failed"; tail -5 "$OUT/bench.err"; exit 1; }
 SHORT="bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-r1-point"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o s -- python3 $SHORT > "$OUT/stats.log" 2>&1 || { echo "kernel-trace failed"; tail -5 "$OUT/stats.log"; exit 1; }
 STATS=$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)

@@ -80,10 +80,63 @@ def test_rank_failure_propagates_nonzero_exit():
 @pytest.mark.gpu
 def test_two_rank_bench_over_gloo_on_one_gpu():
     """The real rank body: two fresh processes sharing the box's GPU, gloo exchange of bf16 predictions."""
-    p, lines = _run(["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--repeats", "1"], 900)
+    p, lines = _run(["--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--repeats", "1", "--full"], 900)
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["config"]["global_batch"] == 8
     assert "gloo" in out["config"]["workload"] and "RCCL" not in out["config"]["workload"]
     assert out["roofline"]["by_kernel"]["voxel_head"]["launches"] == 2
+
+
+def test_plain_run_options():
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    args = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert args.steps == 7 and args.warmup == 2 and args.full is False and args.dump_outputs is None
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full is True
+
+
+def test_dump_outputs_format(tmp_path):
+    """--dump-outputs: float32 files, a fixed sample (same positions every run) and at most 64 MB at the headline's B = 64."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    pred = torch.randn(8, 1000, 1024)
+    bench.dump_outputs(pred, tmp_path / "a")
+    bench.dump_outputs(pred, tmp_path / "b")
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == ["predictions_first4.npy", "predictions_sample.npy"]
+    first4 = np.load(tmp_path / "a" / "predictions_first4.npy")
+    sample = np.load(tmp_path / "a" / "predictions_sample.npy")
+    assert first4.dtype == np.float32 and sample.dtype == np.float32
+    np.testing.assert_array_equal(first4, pred[:4].numpy())
+    assert sample.shape == (bench.DUMP_SAMPLE,) and np.isin(sample, pred.numpy()).all()
+    np.testing.assert_array_equal(sample, np.load(tmp_path / "b" / "predictions_sample.npy"))
+    assert 4 * 1000 * 1024 * 4 + bench.DUMP_SAMPLE * 4 <= 64e6        # B = 64: first four sequences + the sample
+
+    small = torch.randn(1, 10, 12)
+    bench.dump_outputs(small, tmp_path / "c")
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "predictions_sample.npy"), small.reshape(-1).numpy())
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run times the steps and prints the headline; the roofline, side points and CPU baseline belong to --full."""
+    import numpy as np
+
+    p, lines = _run(["--steps", "3", "--warmup", "1", "--repeats", "1", "--dump-outputs", str(tmp_path)], 600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0 and out["dtype"] == "bf16"
+    assert abs(out["value"] - 4 * 1024 / (out["ms_per_step"] * 1e-3)) < 1e-2 * out["value"]
+    assert not {"roofline", "r1_point", "config1_point", "cpu_baseline"} & set(out)
+    first4 = np.load(tmp_path / "predictions_first4.npy")
+    sample = np.load(tmp_path / "predictions_sample.npy")
+    assert first4.shape == (4, 1000, 1024) and sample.shape == (4 * 1000 * 1024,)
+    assert np.isfinite(first4).all() and np.array_equal(sample.reshape(4, 1000, 1024), first4)
