@@ -74,7 +74,11 @@ class BrainModule(nn.Module):
                 metric.update(pred, target, groups=subjects)
                 continue
             if "retrieval" in key:
-                metric.update(pred.mean(dim=-1), target.mean(dim=-1))
+                fused = getattr(metric, "update_bvt", None)   # Rank / TopkAcc: time-means fused into the ranks launch pair
+                if fused is not None:
+                    fused(pred, target)
+                else:
+                    metric.update(pred.mean(dim=-1), target.mean(dim=-1))
             else:
                 metric.update(pred, target)
             self.log(key, metric)

@@ -5,6 +5,8 @@ import pydantic
 
 from .base import (BaseMetricConfig, GroupedMetric, GroupedMetricConfig, MultidimPearsonCorrCoef,  # noqa: F401
                    MultidimPearsonCorrCoefConfig, OnlinePearsonCorr)
+from .metrics import OnlinePearsonCorrConfig, Rank, RankConfig, TopkAcc, TopkAccConfig  # noqa: F401
 
-MetricConfig = tp.Annotated[tp.Union[MultidimPearsonCorrCoefConfig, GroupedMetricConfig],
+MetricConfig = tp.Annotated[tp.Union[MultidimPearsonCorrCoefConfig, GroupedMetricConfig, OnlinePearsonCorrConfig, RankConfig,
+                                     TopkAccConfig],
                             pydantic.Field(discriminator="name")]

@@ -264,6 +264,10 @@ SIGNATURES = {
     "tribe_pearson_from_stats": (C.c_int, [vp, i64, i64, vp, vp]),
     "tribe_pearson_loss_fwd": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i64, i32, vp, vp, sz, vp]),
     "tribe_pearson_loss_workspace_bytes": (sz, [i64]),
+    "tribe_retrieval_prep": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp]),
+    "tribe_retrieval_ranks": (C.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, vp, i32, vp, vp]),
+    "tribe_retrieval_scores": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, i32, vp, vp]),
+    "tribe_rank_reduce": (C.c_int, [vp, i64, f32, vp, vp]),
 }
 
 _lib = None

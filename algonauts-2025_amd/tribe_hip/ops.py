@@ -534,6 +534,106 @@ def pearson_loss(pred: torch.Tensor, true: torch.Tensor, reduction: str = "mean"
 
 
 # --------------------------------------------------------------------------------------
+# retrieval metrics Rank / TopkAcc (csrc/metrics.hip)
+# --------------------------------------------------------------------------------------
+_NORM_KINDS = {None: 0, "x": 1, "y": 2, "xy": 3}
+
+
+def _nvt(x: torch.Tensor, what: str) -> torch.Tensor:
+    """[N, V] -> [N, V, 1] view (T = 1); [N, V, T] as is."""
+    if x.ndim == 2:
+        return x.unsqueeze(-1)
+    if x.ndim != 3:
+        raise ValueError(f"{what}: expected [N, V] or [N, V, T], got {tuple(x.shape)}")
+    return x
+
+
+def retrieval_prep(x: torch.Tensor, y: torch.Tensor | None = None, *, mean: bool = True, norm_x: bool = False,
+                   norm_y: bool = False) -> tuple[torch.Tensor | None, torch.Tensor | None, torch.Tensor | None, torch.Tensor | None]:
+    """Strided f32 [N, V, T] views (or [N, V]) -> (x_mean [N, V], y_mean, x_norm [N], y_norm): means over T and the L2 norms of
+    the mean rows, in one launch for both tensors (y: same shape and strides as x).  Outputs not asked for are None."""
+    _cuda(x, torch.float32, "x", contiguous=False)
+    x3 = _nvt(x, "retrieval_prep")
+    if y is not None:
+        _cuda(y, torch.float32, "y", contiguous=False)
+        N, V, T, sn, sv, st = _bvt_strides(x3, _nvt(y, "retrieval_prep"), "retrieval_prep")
+    else:
+        N, V, T = x3.shape
+        sn, sv, st = x3.stride()
+    if N == 0 or V == 0 or T == 0:
+        raise ValueError(f"retrieval_prep: empty input {tuple(x.shape)}")
+    dev = x.device
+    xm = torch.empty(N, V, dtype=torch.float32, device=dev) if mean else None
+    ym = torch.empty(N, V, dtype=torch.float32, device=dev) if mean and y is not None else None
+    xn = torch.empty(N, dtype=torch.float32, device=dev) if norm_x else None
+    yn = torch.empty(N, dtype=torch.float32, device=dev) if norm_y and y is not None else None
+    check(lib().tribe_retrieval_prep(x.data_ptr(), _p(y), N, V, T, sn, sv, st, _p(xm), _p(ym), _p(xn), _p(yn), _stream()),
+          "tribe_retrieval_prep")
+    return xm, ym, xn, yn
+
+
+def _rows(x: torch.Tensor, name: str) -> torch.Tensor:
+    _cuda(x, torch.float32, name, contiguous=False)
+    if x.ndim != 2 or x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        raise ValueError(f"{name}: expected an f32 [rows, V] matrix with unit column stride, got {tuple(x.shape)} / {x.stride()}")
+    return x
+
+
+def retrieval_ranks(x: torch.Tensor, y: torch.Tensor, y_norm: torch.Tensor, true_idx: torch.Tensor | None = None,
+                    relative: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Rank of every query x [N, V] among the gallery y [M, V] (y_norm [M] from retrieval_prep), true row t(n) = true_idx[n]
+    (int64 [N]) or n.  Writes f32 [N] into `out` (e.g. a slice of a metric's state buffer) or a new tensor."""
+    _rows(x, "x")
+    _rows(y, "y")
+    _cuda(y_norm, torch.float32, "y_norm")
+    (N, V), M = x.shape, y.shape[0]
+    if y.shape[1] != V or y_norm.shape != (M,):
+        raise ValueError(f"retrieval_ranks: x {tuple(x.shape)}, y {tuple(y.shape)}, y_norm {tuple(y_norm.shape)}")
+    if true_idx is None and N != M:
+        raise ValueError(f"retrieval_ranks: without labels queries and gallery must have the same length, got {N} and {M}")
+    if true_idx is not None:
+        _cuda(true_idx, torch.int64, "true_idx")
+        if true_idx.shape != (N,):
+            raise ValueError(f"retrieval_ranks: true_idx must be [{N}], got {tuple(true_idx.shape)}")
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=x.device)
+    _cuda(out, torch.float32, "out")
+    if out.shape != (N,):
+        raise ValueError(f"retrieval_ranks: out must be [{N}], got {tuple(out.shape)}")
+    check(lib().tribe_retrieval_ranks(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), y_norm.data_ptr(), N, M, V, _p(true_idx),
+                                      int(bool(relative)), out.data_ptr(), _stream()), "tribe_retrieval_ranks")
+    return out
+
+
+def retrieval_scores(x: torch.Tensor, y: torch.Tensor, norm_kind: str | None = "y") -> torch.Tensor:
+    """Materialised f32 [N, M] similarity of Rank._compute_sim (norm_kind None | "x" | "y" | "xy"); diagnostic path."""
+    if norm_kind not in _NORM_KINDS:
+        raise ValueError(f"norm must be None, x, y or xy, got {norm_kind}.")
+    _rows(x, "x")
+    _rows(y, "y")
+    (N, V), M = x.shape, y.shape[0]
+    if y.shape[1] != V:
+        raise ValueError(f"retrieval_scores: x {tuple(x.shape)} vs y {tuple(y.shape)}")
+    xn = retrieval_prep(x, mean=False, norm_x=True)[2] if norm_kind in ("x", "xy") else None
+    yn = retrieval_prep(y, mean=False, norm_x=True)[2] if norm_kind in ("y", "xy") else None
+    out = torch.empty(N, M, dtype=torch.float32, device=x.device)
+    check(lib().tribe_retrieval_scores(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), N, M, V, _p(xn), _p(yn),
+                                       _NORM_KINDS[norm_kind], out.data_ptr(), _stream()), "tribe_retrieval_scores")
+    return out
+
+
+def rank_reduce(ranks: torch.Tensor, topk: float = 1.0) -> torch.Tensor:
+    """f32 [4] = {mean, unbiased std, lower median, mean(ranks < topk)} of f32 ranks [n], n > 0 (one launch)."""
+    _cuda(ranks, torch.float32, "ranks")
+    n = ranks.numel()
+    if n == 0:
+        raise ValueError("rank_reduce: no ranks")
+    out = torch.empty(4, dtype=torch.float32, device=ranks.device)
+    check(lib().tribe_rank_reduce(ranks.data_ptr(), n, float(topk), out.data_ptr(), _stream()), "tribe_rank_reduce")
+    return out
+
+
+# --------------------------------------------------------------------------------------
 # measurement hook: HIP events around every GEMM launch, summed per operator role
 # --------------------------------------------------------------------------------------
 def prof_begin(max_records: int = 4096) -> None:

@@ -451,6 +451,23 @@ int tribe_pearson_loss_fwd(const float* pred, const float* truth, int64_t B, int
                            int64_t sb, int64_t sv, int64_t st,
                            int32_t reduction_sum, float* out, void* workspace, size_t workspace_bytes, void* stream);
 size_t tribe_pearson_loss_workspace_bytes(int64_t V);
+/* Retrieval metrics Rank / TopkAcc (modeling_utils/metrics/metrics.py:66-218, fed by pl_module.py:98-99).  No workspace.
+ * prep: x (and y, same shape and strides, or NULL) are strided [N, V, T] f32 views; per row n and tensor:
+ *   *_mean[n][v] = mean_t in[n][v][t] ([N, V] contiguous; NULL: not written),
+ *   *_norm[n]    = || mean row n ||_2 (NULL: not computed).  T = 1 with (sn, sv) = (ld, 1) reads a plain [N, V] matrix. */
+int tribe_retrieval_prep(const float* x, const float* y, int64_t N, int64_t V, int64_t T, int64_t sn, int64_t sv, int64_t st,
+                         float* x_mean, float* y_mean, float* x_norm, float* y_norm, void* stream);
+/* ranks[n] of query x[n] among gallery rows y[0..M) (rows ld elements apart), s[n][m] = dot(x_n, y_m) / (1e-15 + y_norm[m]):
+ * rank = (#{m: s > s[n][t(n)]} + #{m: s >= s[n][t(n)]} - 1) / 2, t(n) = true_idx[n] (NULL: t(n) = n, needs N == M);
+ * rank < 0 (NaN true score) -> N / 2; relative != 0 -> rank / M; t(n) outside [0, M) -> NaN.  No [N, M] buffer is formed. */
+int tribe_retrieval_ranks(const float* x, int64_t ldx, const float* y, int64_t ldy, const float* y_norm, int64_t N, int64_t M,
+                          int64_t V, const int64_t* true_idx, int32_t relative, float* ranks, void* stream);
+/* scores[N][M] = dot(x_n, y_m) * f (Rank._compute_sim): norm_kind 0 none (f = 1), 1 "x" 1/(1e-15 + x_norm[n]),
+ * 2 "y" 1/(1e-15 + y_norm[m]), 3 "xy" 1/(1e-15 + x_norm[n] y_norm[m]).  Diagnostic; "y" scores equal the ones ranks compares. */
+int tribe_retrieval_scores(const float* x, int64_t ldx, const float* y, int64_t ldy, int64_t N, int64_t M, int64_t V,
+                           const float* x_norm, const float* y_norm, int32_t norm_kind, float* scores, void* stream);
+/* out[0..4) = {mean, unbiased std, lower median, mean(ranks < topk)} of ranks[0..n) (ranks >= 0), one launch */
+int tribe_rank_reduce(const float* ranks, int64_t n, float topk, float* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Backward building blocks (pl_module.training_step: loss.backward() of the path).
