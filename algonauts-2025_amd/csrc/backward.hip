@@ -422,10 +422,8 @@ __global__ __launch_bounds__(256) void pearson_loss_bwd_kernel(const float* __re
   const double* s = stats + v * 6;
   const double n = s[5];
   const float mx = (float)(s[0] / n), my = (float)(s[1] / n);
-  const double cov = s[4] - s[0] * s[1] / n;
-  double vx = s[2] - s[0] * s[0] / n, vy = s[3] - s[1] * s[1] / n;
-  vx = vx > 0.0 ? vx : 0.0;
-  vy = vy > 0.0 ? vy : 0.0;
+  const double vx = onepass_centred_ss(s[0], s[2], n), vy = onepass_centred_ss(s[1], s[3], n);
+  const double cov = (vx > 0.0 && vy > 0.0) ? s[4] - s[0] * s[1] / n : 0.0;   // as pearson_loss_final_kernel
   const float sx = sqrtf((float)vx), sy = sqrtf((float)vy);
   const float den = sx * sy + 1e-8f;
   const float k = gs[0] * w;

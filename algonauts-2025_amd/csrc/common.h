@@ -41,6 +41,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+// Centred sum of squares S2 - S1^2 / n of n samples from one-pass f64 sums (Pearson statistics).  Each of the up to n adds behind
+// S1 and S2 may be off by an ulp of its running sum, so a result at or below n * DBL_EPSILON * S2 cannot be told from 0 and is 0:
+// a constant column of ~1e5 samples otherwise leaves rounding noise of either sign here, and r = noise / noise.
+__device__ __forceinline__ double onepass_centred_ss(double s1, double s2, double n) {
+  const double v = s2 - s1 * s1 / n;
+  return v > n * __DBL_EPSILON__ * s2 ? v : 0.0;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));

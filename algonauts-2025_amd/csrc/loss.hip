@@ -189,13 +189,14 @@ __global__ void pearson_from_stats_kernel(const double* __restrict__ stats, int6
   if (i >= n) return;
   const double* s = stats + i * 6;
   const double cnt = s[5];
-  if (cnt < 2.0) { r[i] = __builtin_nanf(""); return; }
+  const double vx = onepass_centred_ss(s[0], s[2], cnt), vy = onepass_centred_ss(s[1], s[3], cnt);
+  // n < 2 or a constant column -> NaN, as scipy / torchmetrics give
+  if (cnt < 2.0 || vx == 0.0 || vy == 0.0) { r[i] = __builtin_nanf(""); return; }
   const double cov = s[4] - s[0] * s[1] / cnt;
-  const double vx = s[2] - s[0] * s[0] / cnt, vy = s[3] - s[1] * s[1] / cnt;
   double v = cov / sqrt(vx * vy);
   if (v > 1.0) v = 1.0;
   if (v < -1.0) v = -1.0;
-  r[i] = (float)v;  // 0/0 -> NaN for a constant column, as scipy / torchmetrics give
+  r[i] = (float)v;
 }
 
 // PearsonLoss (losses.py:17-42): per voxel 1 - cov / (sqrt(Sxx_c) * sqrt(Syy_c) + 1e-8), then mean | sum over voxels
@@ -206,10 +207,9 @@ __global__ __launch_bounds__(256) void pearson_loss_final_kernel(const double* _
   for (int64_t v = threadIdx.x; v < V; v += blockDim.x) {
     const double* s = stats + v * 6;
     const double cnt = s[5];
-    const double cov = s[4] - s[0] * s[1] / cnt;
-    double vx = s[2] - s[0] * s[0] / cnt, vy = s[3] - s[1] * s[1] / cnt;
-    vx = vx > 0.0 ? vx : 0.0;
-    vy = vy > 0.0 ? vy : 0.0;
+    const double vx = onepass_centred_ss(s[0], s[2], cnt), vy = onepass_centred_ss(s[1], s[3], cnt);
+    // |cov| <= sqrt(vx vy): a column without variance has no covariance either (the reference's centred sums give exactly 0)
+    const double cov = (vx > 0.0 && vy > 0.0) ? s[4] - s[0] * s[1] / cnt : 0.0;
     // the reference works in f32: mirror its rounding of the two square roots and of the eps add
     const float xs = sqrtf((float)vx), ys = sqrtf((float)vy);
     const float pcc = (float)cov / (xs * ys + 1e-8f);

@@ -28,6 +28,12 @@ def _as_bvt(x: torch.Tensor, dim: int) -> torch.Tensor:
 
 
 class PearsonLoss(nn.Module):
+    """1 - Pearson r per column (eps 1e-8 in the denominator), mean | sum over columns.
+
+    A column whose one-pass variance is within rounding of 0 counts as constant: its covariance is 0 too.  For a constant
+    prediction column the gradient is the finite term -k / den * (y - mean y) (den = 1e-8): the reference's autograd gives NaN
+    there, because the derivative of sqrt at 0 is infinite and multiplies 0."""
+
     def __init__(self, reduction: str = "mean", dim: int = 1):
         super().__init__()
         self.reduction = reduction

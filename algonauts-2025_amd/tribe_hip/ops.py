@@ -222,10 +222,28 @@ def projector_zero_fwd(BT: int, T: int, n_out: int, x: torch.Tensor, col0: int, 
 # --------------------------------------------------------------------------------------
 # encoder pieces
 # --------------------------------------------------------------------------------------
+def _norm_params(what: str, x: torch.Tensor, w: torch.Tensor | None = None, b: torch.Tensor | None = None,
+                 g: torch.Tensor | None = None) -> int:
+    """Row width of a norm's input, checked against the lengths of its parameters before anything else: the kernels read dim
+    weights (and biases) per row and the gain g[0], so a short vector would be an out-of-bounds read on the device."""
+    for name, t in (("x", x), ("w", w), ("b", b), ("g", g)):
+        if t is not None and not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t)}")
+    dim = x.shape[-1] if x.ndim > 0 else 0
+    if dim == 0:
+        raise ValueError(f"{what}: x must have a non-empty last dimension, got shape {tuple(x.shape)}")
+    for name, t in (("w", w), ("b", b)):
+        if t is not None and t.numel() != dim:
+            raise ValueError(f"{what}: {name} must have dim={dim} elements, got shape {tuple(t.shape)}")
+    if g is not None and g.numel() == 0:
+        raise ValueError(f"{what}: g must hold the gain, got an empty tensor")
+    return dim
+
+
 def scalenorm(x: torch.Tensor, g: torch.Tensor, gain_scale: float, eps: float, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    dim = _norm_params("scalenorm", x, g=g)
     _cuda(x, torch.float32, "x")
     _cuda(g, torch.float32, "g")
-    dim = x.shape[-1]
     rows = x.numel() // dim
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     check(lib().tribe_scalenorm_fwd(x.data_ptr(), rows, dim, g.data_ptr(), gain_scale, eps, y.data_ptr(), _DT[out_dtype], _stream()),
@@ -288,9 +306,9 @@ def attention_relative_key(qkv: torch.Tensor, B: int, T: int, heads: int, dim_he
 
 
 def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    dim = _norm_params("rmsnorm", x, w)
     _cuda(x, torch.float32, "x")
     _cuda(w, torch.float32, "w")
-    dim = x.shape[-1]
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     check(lib().tribe_rmsnorm_fwd(x.data_ptr(), x.numel() // dim, dim, w.data_ptr(), eps, y.data_ptr(), _DT[out_dtype], _stream()),
           "tribe_rmsnorm_fwd")
@@ -298,9 +316,11 @@ def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, out_dtype: torch.dtype
 
 
 def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, eps: float, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    dim = _norm_params("layernorm", x, w, b)
     _cuda(x, torch.float32, "x")
     _cuda(w, torch.float32, "w")
-    dim = x.shape[-1]
+    if b is not None:
+        _cuda(b, torch.float32, "b")
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
     check(lib().tribe_layernorm_fwd(x.data_ptr(), x.numel() // dim, dim, w.data_ptr(), _p(b), eps, y.data_ptr(), _DT[out_dtype],
                                     _stream()), "tribe_layernorm_fwd")
@@ -795,11 +815,13 @@ def quantize_fp8(x: torch.Tensor, scale: float, K_pad: int | None = None) -> tor
 
 def norm_quantize_fp8(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, eps: float, scale: float, layernorm: bool) -> torch.Tensor:
     """quantize_fp8(rmsnorm(x) | layernorm(x) in bf16, scale) in one pass: x f32 [..., dim] -> uint8 [rows, dim] of e4m3 bytes."""
+    dim = _norm_params("norm_quantize_fp8", x, w, b)
     _cuda(x, torch.float32, "x")
     _cuda(w, torch.float32, "w")
+    if b is not None:
+        _cuda(b, torch.float32, "b")
     if not scale > 0:
         raise ValueError(f"norm_quantize_fp8: scale must be positive, got {scale}")
-    dim = x.shape[-1]
     rows = x.numel() // dim
     out = torch.empty(rows, dim, dtype=torch.uint8, device=x.device)
     check(lib().tribe_norm_quantize_fp8_fwd(x.data_ptr(), rows, dim, w.data_ptr(), _p(b), int(layernorm), eps, 1.0 / scale, out.data_ptr(),

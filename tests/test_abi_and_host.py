@@ -211,6 +211,30 @@ def test_hot_path_refuses_cpu_tensors():
         m({"text": torch.zeros(1, 1, 8, 4), "subject_id": torch.zeros(1, 1, dtype=torch.long)})
 
 
+def test_norm_wrappers_check_parameter_lengths():
+    """ops.rmsnorm / layernorm / scalenorm / norm_quantize_fp8 refuse a weight or bias whose length is not the row width, and an
+    empty gain, before anything reaches the device (the kernels would read past a short vector).  Every call here fails validation."""
+    from tribe_hip import ops
+
+    x = torch.zeros(3, 8)
+    w, b = torch.ones(8), torch.zeros(8)
+    bad_calls = {
+        "rmsnorm short w": lambda: ops.rmsnorm(x, torch.ones(7), 1e-5),
+        "rmsnorm long w": lambda: ops.rmsnorm(x, torch.ones(9), 1e-5),
+        "rmsnorm empty row": lambda: ops.rmsnorm(torch.zeros(3, 0), torch.ones(0), 1e-5),
+        "layernorm short w": lambda: ops.layernorm(x, torch.ones(4), b, 1e-5),
+        "layernorm short b": lambda: ops.layernorm(x, w, torch.zeros(7), 1e-5),
+        "layernorm 2-D b": lambda: ops.layernorm(x, w, torch.zeros(2, 8), 1e-5),
+        "scalenorm empty g": lambda: ops.scalenorm(x, torch.ones(0), 1.0, 1e-5),
+        "norm_quantize_fp8 short w": lambda: ops.norm_quantize_fp8(x, torch.ones(4), None, 1e-5, 0.1, False),
+        "norm_quantize_fp8 short b": lambda: ops.norm_quantize_fp8(x, w, torch.zeros(4), 1e-5, 0.1, True),
+    }
+    for what, call in bad_calls.items():
+        with pytest.raises(ValueError, match="elements|empty|non-empty"):
+            call()
+            pytest.fail(f"{what} was accepted")
+
+
 def test_missing_library_fails_loudly(tmp_path):
     code = ("import sys; sys.path.insert(0, %r); from tribe_hip import _lib; _lib.lib()" % str(ROOT / "algonauts-2025_amd"))
     env = {"TRIBE_HIP_LIB": str(tmp_path / "nope.so"), "PATH": "/usr/bin:/bin"}

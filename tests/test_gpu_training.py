@@ -270,20 +270,30 @@ def test_slab_scatter_sum_is_the_ordered_sum():
 @pytest.mark.parametrize("cfg_kw", [{}, {"layer_aggregation": "mean", "subject_embedding": True}, {"feature_aggregation": "sum"}])
 def test_training_step_gradients_vs_oracle(cfg_kw):
     """BrainModule.training_step + loss.backward(): loss and every parameter gradient vs the fp32 CPU oracle graph."""
+    _training_step_gradients_vs_oracle(cfg_kw, V=50, Tout=10, S=3, B=4, T=31, hidden=768, depth=2, heads=4)
+
+
+def test_training_step_gradients_vs_oracle_production_width():
+    """The same at the width the benchmarked model trains at: hidden 3072 (the NV 12 ScaleNorm backward, FF inner 12288), 8 heads of
+    dim_head 384, V = 1000 voxels, 4 subjects, T = 298 steps pooled to 100 TRs (ragged attention and GEMM tiles).  The feature dims
+    stay small so that the CPU oracle stays cheap."""
+    _training_step_gradients_vs_oracle({}, V=1000, Tout=100, S=4, B=2, T=298, hidden=3072, depth=1, heads=8)
+
+
+def _training_step_gradients_vs_oracle(cfg_kw, V, Tout, S, B, T, hidden, depth, heads):
     from algonauts2025.model import FmriEncoderConfig
     from algonauts2025.pl_module import BrainModule
     from data_utils.dataloader import SegmentData
     from modeling_utils.losses import TorchLossConfig
 
     fdims = {"text": (2, 40), "audio": (2, 24), "video": (2, 33)}
-    V, Tout, S, B, T = 50, 10, 3, 4, 31
-    dims = tribe_ref.EncoderDims(hidden=768, depth=2, heads=4)
+    dims = tribe_ref.EncoderDims(hidden=hidden, depth=depth, heads=heads)
     ref = tribe_ref.FmriEncoderRef(fdims, V, Tout, S, layer_aggregation=cfg_kw.get("layer_aggregation", "cat"),
                                    feature_aggregation=cfg_kw.get("feature_aggregation", "cat"),
                                    subject_embedding=cfg_kw.get("subject_embedding", False), dims=dims).train()
     with torch.no_grad():
         tribe_ref.fill_params_(ref, seed=2)
-    model = FmriEncoderConfig(n_subjects=S, hidden=768, depth=2, heads=4, **cfg_kw).build(fdims, V, Tout)
+    model = FmriEncoderConfig(n_subjects=S, hidden=hidden, depth=depth, heads=heads, **cfg_kw).build(fdims, V, Tout)
     model.load_state_dict(ref.state_dict())
     model = model.cuda().train()
     data = tribe_ref.synthetic_batch(B, T, fdims, S, seed=4)
