@@ -45,9 +45,23 @@ class BrainModule(nn.Module):
     def forward(self, batch: SegmentData) -> torch.Tensor:
         return self.model(batch)
 
+    def _hip_loss(self) -> nn.Module | None:
+        """The HIP counterpart of a stock torch loss (modeling_utils.losses.hip_loss_for), resolved once and again whenever `self.loss`
+        is replaced or its hyper-parameters change.  `self.loss` itself stays the module the caller passed in."""
+        loss = self.loss
+        key = (type(loss), getattr(loss, "reduction", None), getattr(loss, "beta", None), getattr(loss, "delta", None))
+        cached = self.__dict__.get("_hip_loss_cache")
+        if cached is None or cached[0] is not loss or cached[1] != key:
+            from modeling_utils.losses import hip_loss_for
+
+            cached = self.__dict__["_hip_loss_cache"] = (loss, key, hip_loss_for(loss))
+        return cached[2]
+
     def _primary_loss(self, pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-        """pl_module.py:54-56 without the two transposing copies when the loss understands [B, V, T'] directly."""
+        """pl_module.py:54-56 without the two transposing copies when the loss, or its HIP counterpart, understands [B, V, T'] directly."""
         fused = getattr(self.loss, "forward_bvt", None)
+        if fused is None and pred.is_cuda and (hip := self._hip_loss()) is not None:
+            fused = hip.forward_bvt
         if fused is not None:
             return fused(pred, target)
         n_out = pred.shape[1]   # foreign loss module: materialise the "b d t -> (b t) d" flatten it expects

@@ -630,6 +630,26 @@ class MSE(torch.autograd.Function):
         return dp, None
 
 
+class ElemLoss(torch.autograd.Function):
+    """ops.elem_loss (L1 / SmoothL1 / Huber / MSE, mean | sum) with its HIP backward; no gradient for the target, as in `MSE`."""
+
+    @staticmethod
+    def forward(ctx, pred, true, kind: str, param: float, reduction: str):
+        pred, true = pred.contiguous(), true.contiguous()
+        ctx.save_for_backward(pred, true)
+        ctx.kind, ctx.param, ctx.reduction = kind, float(param), reduction
+        return ops.elem_loss(pred, true, kind, param, reduction)
+
+    @staticmethod
+    def backward(ctx, g):
+        pred, true = ctx.saved_tensors
+        dp = torch.empty_like(pred)
+        g = g.reshape(1).to(torch.float32).contiguous()
+        check(lib().tribe_elem_loss_bwd(pred.data_ptr(), true.data_ptr(), pred.numel(), ops.ELEM_LOSS_KINDS[ctx.kind], ctx.param,
+                                        ops.ELEM_LOSS_REDUCTIONS[ctx.reduction], g.data_ptr(), dp.data_ptr(), _s()), "tribe_elem_loss_bwd")
+        return dp, None, None, None, None
+
+
 class PearsonLossFn(torch.autograd.Function):
     """PearsonLoss over the '(b t) d' view of strided [B, V, T] tensors (losses.py:17-42)."""
 

@@ -59,5 +59,6 @@ class TorchLossConfig(BaseLossConfig):
         kwargs = self.kwargs | kwargs
         if self.name == "MSELoss" and kwargs.get("reduction", "mean") == "mean" and not (set(kwargs) - {"reduction"}):
             return losses.MSELoss()  # the default loss (defaults.py:125) runs in HIP
-        # SmoothL1Loss / HuberLoss etc. (run_ensemble.py grids): stock torch modules, outside the HIP scope
+        # everything else is the stock torch module, as in the reference.  For L1Loss / SmoothL1Loss / HuberLoss (run_ensemble.py grids) and
+        # MSELoss(reduction="sum") BrainModule runs the HIP counterpart that losses.hip_loss_for finds; other torch losses run as they are
         return getattr(nn, self.name)(**kwargs)

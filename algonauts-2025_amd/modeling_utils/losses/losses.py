@@ -2,12 +2,14 @@
 
 `PearsonLoss` mirrors /root/reference/modeling_utils/modeling_utils/losses/losses.py:11-42
 (1 - per-column Pearson with eps 1e-8, mean | sum over columns).  `MSELoss` is the HIP
-counterpart of `torch.nn.MSELoss()` selected by defaults.py:125.
+counterpart of `torch.nn.MSELoss()` selected by defaults.py:125; `L1Loss`, `SmoothL1Loss` and
+`HuberLoss` are those of the torch modules of the same name (grids/run_ensemble.py draws the last
+two), and `hip_loss_for` maps a stock torch module to its counterpart.
 
-Both accept what the reference passes -- two [N, V] matrices, columns = voxels -- and, as the
+All accept what the reference passes -- two [N, V] matrices, columns = voxels -- and, as the
 fast path used by BrainModule, the un-flattened [B, V, T'] pair via `forward_bvt` (the '(b t) d'
 flatten of pl_module.py:54-55 is a pure re-indexing of the same sums and is never materialised).
-Both are differentiable (HIP backward kernels, modeling_utils/autograd.py).
+All are differentiable (HIP backward kernels, modeling_utils/autograd.py).
 """
 
 from __future__ import annotations
@@ -52,16 +54,88 @@ class PearsonLoss(nn.Module):
         return self.forward_bvt(_as_bvt(x.float(), self.dim), _as_bvt(y.float(), self.dim))
 
 
-class MSELoss(nn.Module):
-    """mean((pred - true)^2) over all elements (torch.nn.MSELoss(reduction='mean'))."""
+def _check_reduction(name: str, reduction: str) -> None:
+    if reduction == "none":
+        raise NotImplementedError(f"the HIP {name} implements reduction='mean' and 'sum' (what the reference's grids configure), not 'none'")
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"{reduction} is not a valid value for reduction")
+
+
+class _ElemLoss(nn.Module):
+    """An element-wise loss reduced over all elements: one HIP forward (ops.elem_loss) and one backward (autograd.ElemLoss).  The
+    reduction does not depend on the element order, so [N, V] matrices and the un-flattened [B, V, T'] pair take the same path."""
+
+    kind: str
 
     def __init__(self, reduction: str = "mean"):
         super().__init__()
-        if reduction != "mean":
-            raise NotImplementedError("the HIP MSELoss implements reduction='mean' (the only one the reference configures)")
+        _check_reduction(type(self).__name__, reduction)
         self.reduction = reduction
 
+    def _param(self) -> float:
+        return 0.0
+
     def forward(self, pred: torch.Tensor, true: torch.Tensor) -> torch.Tensor:
+        name = type(self).__name__
+        if pred.shape != true.shape:
+            raise ValueError(f"{name}: shape mismatch {tuple(pred.shape)} vs {tuple(true.shape)}")
+        _check_reduction(name, self.reduction)
+        if torch.is_grad_enabled() and pred.requires_grad:
+            from ..autograd import ElemLoss
+
+            return ElemLoss.apply(pred.float(), true.float(), self.kind, self._param(), self.reduction)
+        return ops.elem_loss(pred.float().contiguous(), true.float().contiguous(), self.kind, self._param(), self.reduction)
+
+    forward_bvt = forward
+
+
+class L1Loss(_ElemLoss):
+    """mean | sum of |pred - true| (torch.nn.L1Loss); the gradient is sign(pred - true), 0 where they are equal."""
+
+    kind = "l1"
+
+
+class SmoothL1Loss(_ElemLoss):
+    """torch.nn.SmoothL1Loss: 0.5 d^2 / beta for |d| < beta, |d| - 0.5 beta otherwise; beta == 0 is L1Loss.  A negative beta raises here, at
+    construction, with the words torch uses at call time."""
+
+    kind = "smooth_l1"
+
+    def __init__(self, reduction: str = "mean", beta: float = 1.0):
+        super().__init__(reduction)
+        if beta < 0:
+            raise ValueError("smooth_l1_loss does not support negative values for beta.")
+        self.beta = beta
+
+    def _param(self) -> float:
+        return float(self.beta)
+
+
+class HuberLoss(_ElemLoss):
+    """torch.nn.HuberLoss: 0.5 d^2 for |d| <= delta, delta (|d| - 0.5 delta) otherwise.  Unlike torch, whose module constructs with any delta
+    and fails at the first call, delta <= 0 raises here at construction (with torch's call-time words)."""
+
+    kind = "huber"
+
+    def __init__(self, reduction: str = "mean", delta: float = 1.0):
+        super().__init__(reduction)
+        if delta <= 0:
+            raise ValueError("huber_loss does not support non-positive values for delta.")
+        self.delta = delta
+
+    def _param(self) -> float:
+        return float(self.delta)
+
+
+class MSELoss(_ElemLoss):
+    """mean | sum of (pred - true)^2 over all elements (torch.nn.MSELoss).  'mean', the reference's default loss, keeps its own entry
+    points (tribe_mse_fwd / tribe_mse_bwd); 'sum' runs through the element-wise family."""
+
+    kind = "mse"
+
+    def forward(self, pred: torch.Tensor, true: torch.Tensor) -> torch.Tensor:
+        if self.reduction != "mean":
+            return super().forward(pred, true)
         if pred.shape != true.shape:
             raise ValueError(f"MSELoss: shape mismatch {tuple(pred.shape)} vs {tuple(true.shape)}")
         if torch.is_grad_enabled() and pred.requires_grad:
@@ -71,3 +145,20 @@ class MSELoss(nn.Module):
         return ops.mse(pred.float().contiguous(), true.float().contiguous())
 
     forward_bvt = forward
+
+
+def hip_loss_for(module: nn.Module) -> nn.Module | None:
+    """The HIP counterpart, with the same hyper-parameters, of a stock torch.nn.MSELoss / L1Loss / SmoothL1Loss / HuberLoss whose reduction
+    is 'mean' or 'sum'; None for everything else (subclasses, reduction='none', other losses, modules that already have forward_bvt)."""
+    if getattr(module, "reduction", None) not in ("mean", "sum"):
+        return None
+    kind = type(module)
+    if kind is nn.MSELoss:
+        return MSELoss(reduction=module.reduction)
+    if kind is nn.L1Loss:
+        return L1Loss(reduction=module.reduction)
+    if kind is nn.SmoothL1Loss and module.beta >= 0:
+        return SmoothL1Loss(reduction=module.reduction, beta=module.beta)
+    if kind is nn.HuberLoss and module.delta > 0:
+        return HuberLoss(reduction=module.reduction, delta=module.delta)
+    return None   # an invalid beta / delta is left to torch, which reports it at the call

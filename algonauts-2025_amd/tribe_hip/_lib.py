@@ -222,6 +222,7 @@ SIGNATURES = {
     "tribe_softmax_bwd": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, f32, vp, i64, vp]),
     "tribe_softmax_fwd": (C.c_int, [vp, i64, i64, i64, vp, i64, i64, vp]),
     "tribe_mse_bwd": (C.c_int, [vp, vp, i64, vp, vp, vp]),
+    "tribe_elem_loss_bwd": (C.c_int, [vp, vp, i64, i32, f32, i32, vp, vp, vp]),
     "tribe_adaptive_avg_pool_bwd": (C.c_int, [vp, i64, i64, i64, vp, vp]),
     "tribe_rowsum_scatter": (C.c_int, [vp, i64, i64, i64, vp, vp, vp]),
     "tribe_slab_scatter_sum": (C.c_int, [vp, i64, i64, vp, vp, vp]),
@@ -260,6 +261,8 @@ SIGNATURES = {
     "tribe_adaptive_avg_pool_fwd": (C.c_int, [vp, i64, i64, vp, i64, vp]),
     "tribe_mse_fwd": (C.c_int, [vp, vp, i64, vp, vp, sz, vp]),
     "tribe_mse_workspace_bytes": (sz, [i64]),
+    "tribe_elem_loss_fwd": (C.c_int, [vp, vp, i64, i32, f32, i32, vp, vp, sz, vp]),
+    "tribe_elem_loss_workspace_bytes": (sz, [i64]),
     "tribe_pearson_stats_update": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i64, vp, i64, vp, vp]),
     "tribe_pearson_from_stats": (C.c_int, [vp, i64, i64, vp, vp]),
     "tribe_pearson_loss_fwd": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i64, i32, vp, vp, sz, vp]),

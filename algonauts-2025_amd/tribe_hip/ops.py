@@ -503,6 +503,29 @@ def mse(pred: torch.Tensor, true: torch.Tensor) -> torch.Tensor:
     return out
 
 
+ELEM_LOSS_KINDS = {"l1": 0, "smooth_l1": 1, "huber": 2, "mse": 3}        # enum tribe_loss_kind
+ELEM_LOSS_REDUCTIONS = {"mean": 0, "sum": 1}                             # enum tribe_loss_reduction
+
+
+def elem_loss(pred: torch.Tensor, true: torch.Tensor, kind: str, param: float = 1.0, reduction: str = "mean") -> torch.Tensor:
+    """nn.L1Loss / SmoothL1Loss(beta=param) / HuberLoss(delta=param) / MSELoss over all elements of two equal-shape contiguous f32 tensors
+    (f32 scalar).  The element order does not matter, so a [B, V, T'] pair is read in place."""
+    _cuda(pred, torch.float32, "pred")
+    _cuda(true, torch.float32, "true")
+    if pred.shape != true.shape:
+        raise ValueError(f"elem_loss: shape mismatch {tuple(pred.shape)} vs {tuple(true.shape)}")
+    if kind not in ELEM_LOSS_KINDS:
+        raise ValueError(f"elem_loss: kind must be one of {sorted(ELEM_LOSS_KINDS)}, got {kind!r}")
+    if reduction not in ELEM_LOSS_REDUCTIONS:
+        raise ValueError(f"elem_loss: reduction must be 'mean' or 'sum', got {reduction!r}")
+    n = pred.numel()
+    out = torch.empty((), dtype=torch.float32, device=pred.device)
+    ws = workspace(lib().tribe_elem_loss_workspace_bytes(n), pred.device, "loss")
+    check(lib().tribe_elem_loss_fwd(pred.data_ptr(), true.data_ptr(), n, ELEM_LOSS_KINDS[kind], float(param), ELEM_LOSS_REDUCTIONS[reduction],
+                                    out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "tribe_elem_loss_fwd")
+    return out
+
+
 def _bvt_strides(pred: torch.Tensor, true: torch.Tensor, what: str) -> tuple[int, int, int, int, int, int]:
     """Accept any strided 3-D [B, V, T] view (e.g. the transpose of a '(b t) d' matrix) -- no copy is made."""
     if pred.shape != true.shape or pred.ndim != 3:

@@ -437,6 +437,16 @@ int tribe_adaptive_avg_pool_fwd(const float* x, int64_t rows, int64_t T_in, floa
 int tribe_mse_fwd(const float* pred, const float* truth, int64_t n, float* out,
                   void* workspace, size_t workspace_bytes, void* stream);
 size_t tribe_mse_workspace_bytes(int64_t n);
+/* nn.L1Loss / nn.SmoothL1Loss(beta) / nn.HuberLoss(delta) / nn.MSELoss over all n elements of two flat f32 streams (the losses of the
+ * run_ensemble.py grid; MSE here serves reduction="sum", the default MSELoss() stays on tribe_mse_fwd).  With d = pred - true:
+ *   L1: |d|;  Huber: m (|d| - m / 2), m = min(|d|, delta);  SmoothL1: Huber(beta) / beta, and L1 for beta == 0;  MSE: d^2.
+ * param = beta (SmoothL1, >= 0) or delta (Huber, > 0), ignored otherwise.  out[0] = mean | sum (f32 scalar); the partial sums are
+ * added in a fixed order, so equal inputs give equal bits.  Pointers need 4-byte alignment only (16-byte aligned ones stream float4). */
+enum tribe_loss_kind { TRIBE_LOSS_L1 = 0, TRIBE_LOSS_SMOOTH_L1 = 1, TRIBE_LOSS_HUBER = 2, TRIBE_LOSS_MSE = 3 };
+enum tribe_loss_reduction { TRIBE_REDUCE_MEAN = 0, TRIBE_REDUCE_SUM = 1 };
+int tribe_elem_loss_fwd(const float* pred, const float* truth, int64_t n, int32_t kind, float param, int32_t reduction, float* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+size_t tribe_elem_loss_workspace_bytes(int64_t n);
 /* accumulate f64 sufficient statistics per (group, voxel):
  *   stats[g][v][0..5] += {sum x, sum y, sum x^2, sum y^2, sum xy, count}
  * x = pred, y = true, over rows b with group[b] == g (group == NULL: all rows -> g = 0) and all t.
@@ -497,6 +507,10 @@ int tribe_softmax_bwd(const uint16_t* P, const float* dP, int64_t rows, int64_t 
 int tribe_softmax_fwd(const float* S, int64_t rows, int64_t T, int64_t ld_s, uint16_t* P, int64_t T_pad, int64_t ld_p, void* stream);
 /* d pred = gscale[0] * 2 / n * (pred - true)   (nn.MSELoss backward) */
 int tribe_mse_bwd(const float* pred, const float* truth, int64_t n, const float* gscale, float* dpred, void* stream);
+/* d pred = gscale[0] * k * d value / d pred of tribe_elem_loss_fwd, k = 1 / n (mean) | 1 (sum):  L1 sign(d) (0 at d == 0),
+ * Huber clamp(d, -delta, delta), SmoothL1 clamp(d, -beta, beta) / beta, MSE 2 d.  gscale is a device scalar. */
+int tribe_elem_loss_bwd(const float* pred, const float* truth, int64_t n, int32_t kind, float param, int32_t reduction,
+                        const float* gscale, float* dpred, void* stream);
 /* adaptive average pool backward: dx[r, t] = sum_{i: t in window i} dy[r, i] / |window i| */
 int tribe_adaptive_avg_pool_bwd(const float* dy, int64_t rows, int64_t T_in, int64_t T_out, float* dx, void* stream);
 /* out[idx[b], v] += sum_t x[b, v, t]   (SubjectLayers bias gradient) */
