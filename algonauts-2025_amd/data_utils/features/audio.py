@@ -2,7 +2,8 @@
 
 Mirror of the reference plugin `Wav2VecBert` (/root/reference/data_utils/data_utils/features/audio.py:27-263): a 30-60 s
 waveform chunk is resampled to 16 kHz, z-scored and turned into 160-dim filterbank features by the HF SeamlessM4T
-feature extractor (audio.py:222-234, host side, out of scope like the reference's julius / soundfile IO);
+feature extractor (audio.py:222-234; on the host by default, or on the GPU by `HipFbank` = `tribe_fbank_fwd` with
+`frontend="hip"`; resampling and soundfile IO stay on the host, like the reference's julius);
 `Wav2Vec2BertModel(features, output_hidden_states=True)` (audio.py:253-263) yields 25 hidden states `[T@50Hz, 1024]`,
 which are resampled to 2 Hz by nearest-neighbour `F.interpolate` (audio.py:163-171) -> `[25, 1024, 2*duration]`.
 
@@ -22,6 +23,7 @@ import torch
 
 from tribe_hip import ops
 from tribe_hip._lib import ConformerLayer, W2vBertDesc, check, lib
+from tribe_hip.ops import fbank_frame_count, kaldi_mel_filters, povey_window  # noqa: F401  (host helpers of the front end)
 
 from .plugin import HbmFeaturePlugin
 
@@ -156,15 +158,44 @@ class HipWav2Vec2Bert:
         return states.permute(1, 0, 3, 2).contiguous()  # [B, n_states, dim, n_out]
 
 
+class HipFbank:
+    """The filterbank front end of w2v-bert-2.0 on the GPU (`ops.w2vbert_fbank`): SeamlessM4TFeatureExtractor at its defaults
+    (80 mel bins, stride 2, 16 kHz), usable wherever the plugin takes a `feature_extractor`.  Called like the HF class on ONE
+    waveform [n] or [n, channels] (numpy, host or device tensor; a host waveform is uploaded once) or on a list of them; returns
+    `{"input_features": f32 [B, T_max, 160] on the GPU, "lengths": each chunk's T}`.  `zscore=True` runs the reference's
+    `_preprocess_wav` (channel mean, z-score over the chunk) on the GPU first."""
+
+    def __init__(self, feature_size: int = 80, sampling_rate: int = 16_000, num_mel_bins: int = 80, padding_value: float = 0.0,
+                 stride: int = 2, device: str | torch.device = "cuda"):
+        if (feature_size, sampling_rate, num_mel_bins, padding_value, stride) != (80, 16_000, 80, 0.0, 2):
+            raise NotImplementedError("only the w2v-bert-2.0 front end (80 mel bins, stride 2, 16 kHz, zero padding) is built")
+        self.feature_size, self.sampling_rate, self.num_mel_bins, self.padding_value, self.stride = 80, 16_000, 80, 0.0, 2
+        self.device = torch.device(device)
+
+    def __call__(self, raw_speech: tp.Any, sampling_rate: int | None = None, zscore: bool = False, **kwargs: tp.Any) -> dict[str, tp.Any]:
+        if sampling_rate is not None and sampling_rate != self.sampling_rate:
+            raise ValueError(f"HipFbank works at {self.sampling_rate} Hz, got a waveform sampled at {sampling_rate} Hz")
+        chunks = list(raw_speech) if isinstance(raw_speech, (list, tuple)) else [raw_speech]
+        dev = [torch.as_tensor(c, dtype=torch.float32).to(self.device).contiguous() for c in chunks]
+        for c in dev:
+            fbank_frame_count(int(c.shape[0]) if c.ndim else 0)          # ValueError below one frame, before anything is launched
+        features, lengths = ops.w2vbert_fbank(dev, zscore=zscore)
+        return {"input_features": features, "lengths": lengths}
+
+
 class Wav2VecBert(HbmFeaturePlugin):
     """The reference's audio feature (audio.py:27-263) on the HIP conformer forward: fields `name`, `layers`,
     `layer_aggregation`, `device`, `infra`; `prepare`, `__call__ -> Tensor[L, D, T]`, `_get_data -> [25, 1024, T_event@2Hz]`
-    per Sound event (item uid `filepath_offset_duration`, audio.py:145-149).  Waveform IO (`event.read()`), resampling and the
-    HF filterbank front end stay on the host as in the reference (third-party there too); everything from `input_features`
-    on -- 24 conformer layers, all 25 hidden states, the nearest-neighbour resampling to 2 Hz -- is one C call."""
+    per Sound event (item uid `filepath_offset_duration`, audio.py:145-149).  Waveform IO (`event.read()`) and resampling stay
+    on the host as in the reference (third-party there too).  `frontend` selects who turns the 16 kHz waveform into
+    `input_features`: "hf" (default) is the reference's route -- `_preprocess_wav` in torch and the HF filterbank extractor on
+    the host, then one upload of the features; "hip" uploads the waveform once and runs the channel mean, the z-score and the
+    whole filterbank (`HipFbank`) on the GPU, so the features never exist on the host.  Everything from `input_features` on
+    -- 24 conformer layers, all 25 hidden states, the nearest-neighbour resampling to 2 Hz -- is one C call either way."""
 
     name: tp.Literal["Wav2VecBert"] = "Wav2VecBert"
     pretrained: str = "facebook/w2v-bert-2.0"             # audio.py:47,222; resolved from the local HF cache only
+    frontend: tp.Literal["hf", "hip"] = "hf"              # a route, not a result: kept out of the class uid like `device`
     _EVENT_TYPE: tp.ClassVar[str] = "Sound"
     _KIND: tp.ClassVar[str] = "sampled"
     _model: tp.Any = pydantic.PrivateAttr(default=None)
@@ -195,7 +226,13 @@ class Wav2VecBert(HbmFeaturePlugin):
             self._feature_extractor = self._get_feature_extractor()
         return self._feature_extractor
 
+    @classmethod
+    def _exclude_from_cls_uid(cls) -> list[str]:
+        return super()._exclude_from_cls_uid() + ["frontend"]
+
     def _get_feature_extractor(self) -> tp.Any:
+        if self.frontend == "hip":
+            return HipFbank()
         from transformers import AutoFeatureExtractor, SeamlessM4TFeatureExtractor
 
         try:
@@ -237,6 +274,14 @@ class Wav2VecBert(HbmFeaturePlugin):
         """audio.py:253-263 + 163-171 in one launch sequence: f32 [n_states, dim, timepoints] on the GPU."""
         return self.model.hidden_states_resampled(self._get_features(wav), timepoints)[0]
 
+    def _process_wav_hip(self, wav: torch.Tensor, timepoints: int) -> torch.Tensor:
+        """`_preprocess_wav` + `_get_features` + `_process_wav` without the host: wav f32 [n, channels] is uploaded once."""
+        fe = self.feature_extractor
+        if not isinstance(fe, HipFbank):
+            raise TypeError(f'frontend="hip" needs a HipFbank feature extractor, got {type(fe).__name__}')
+        feats = fe(wav.to(self.model.device), sampling_rate=fe.sampling_rate, zscore=True)["input_features"]
+        return self.model.hidden_states_resampled(feats, timepoints)[0]
+
     def _compute(self, events: list[tp.Any]) -> tp.Iterator[np.ndarray]:
         from ..base import Frequency
 
@@ -249,5 +294,9 @@ class Wav2VecBert(HbmFeaturePlugin):
                 wav, sfreq = torch.as_tensor(got, dtype=torch.float32), event.frequency
             if wav.ndim == 1:
                 wav = wav[:, None]
-            wav = self._preprocess_wav(self._resample_wav(wav, sfreq, self._input_frequency))
-            yield self._process_wav(wav, Frequency(2.0).to_ind(event.duration)).cpu().numpy()
+            wav = self._resample_wav(wav, sfreq, self._input_frequency)
+            timepoints = Frequency(2.0).to_ind(event.duration)
+            if self.frontend == "hip":
+                yield self._process_wav_hip(wav, timepoints).cpu().numpy()
+            else:
+                yield self._process_wav(self._preprocess_wav(wav), timepoints).cpu().numpy()

@@ -7,6 +7,7 @@ from __future__ import annotations
 import ctypes as C
 import typing as tp
 
+import numpy as _np
 import torch
 
 from . import _lib
@@ -876,3 +877,77 @@ def gemm_fp8_nt(a: torch.Tensor, b: torch.Tensor, alpha: float, *, bias: torch.T
         d.res, d.ldres = _cuda(res, torch.float32, "res").data_ptr(), N
     check(lib().tribe_gemm_fp8(C.byref(d), _stream()), "tribe_gemm_fp8")
     return out
+
+
+# --------------------------------------------------------------------------------------
+# Wav2Vec-BERT audio front end: waveform -> filterbank features (csrc/fbank.hip)
+# --------------------------------------------------------------------------------------
+FBANK_WIN, FBANK_HOP, FBANK_NFFT, FBANK_MEL, FBANK_STRIDE = 400, 160, 512, 80, 2    # SeamlessM4TFeatureExtractor defaults, 16 kHz
+FBANK_MAX_CHUNKS = 32                                                               # TRIBE_FBANK_MAX_CHUNKS
+
+
+def fbank_frame_count(n: int) -> int:
+    """Frames of 400 samples every 160 in a waveform of n samples (no centring); the features have ceil(F / 2) rows."""
+    if n < FBANK_WIN:
+        raise ValueError(f"fbank: a waveform of {n} samples is shorter than one frame ({FBANK_WIN})")
+    return 1 + (n - FBANK_WIN) // FBANK_HOP
+
+
+def povey_window() -> _np.ndarray:
+    """Kaldi's Povey window, f64 [400]: hann(400, symmetric) ** 0.85."""
+    return _np.power(_np.hanning(FBANK_WIN), 0.85)
+
+
+def kaldi_mel_filters() -> _np.ndarray:
+    """80 triangular filters on Kaldi's mel scale 1127 ln(1 + f / 700), 20 Hz to 8 kHz, triangles drawn in mel space, no
+    area normalisation: f64 [257, 80] over the bins of a 512-point DFT at 16 kHz."""
+    def to_mel(f):
+        return 1127.0 * _np.log(1.0 + f / 700.0)
+
+    n_bins = FBANK_NFFT // 2 + 1
+    centres = _np.linspace(to_mel(20.0), to_mel(8000.0), FBANK_MEL + 2)
+    bins = to_mel(16_000 / FBANK_NFFT * _np.arange(n_bins))
+    width = _np.diff(centres)
+    slopes = centres[None, :] - bins[:, None]
+    down, up = -slopes[:, :-2] / width[:-1], slopes[:, 2:] / width[1:]
+    return _np.maximum(0.0, _np.minimum(down, up))
+
+
+_FBANK_TABLES: dict[int, tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def _fbank_tables(device: torch.device) -> tuple[torch.Tensor, torch.Tensor]:
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _FBANK_TABLES:
+        _FBANK_TABLES[key] = (torch.from_numpy(povey_window().astype(_np.float32)).to(device),
+                              torch.from_numpy(_np.ascontiguousarray(kaldi_mel_filters().astype(_np.float32))).to(device))
+    return _FBANK_TABLES[key]
+
+
+def w2vbert_fbank(wavs: torch.Tensor | tp.Sequence[torch.Tensor], zscore: bool = True) -> tuple[torch.Tensor, list[int]]:
+    """16 kHz waveform chunk(s) f32 [n] or [n, C] (sample-major) -> (input_features f32 [B, T_max, 160], each chunk's T).
+    zscore: the reference's `_preprocess_wav` first (mean over channels, z-score over the chunk); without it a multi-channel
+    chunk is still averaged over its channels.  Chunks of different lengths run in one launch sequence; rows past a chunk's T
+    are zero, and a chunk's rows are the same bits whatever else is in the batch."""
+    chunks = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
+    if not 1 <= len(chunks) <= FBANK_MAX_CHUNKS:
+        raise ValueError(f"w2vbert_fbank: {len(chunks)} chunks (1 to {FBANK_MAX_CHUNKS} per call)")
+    for i, w in enumerate(chunks):
+        _cuda(w, torch.float32, f"wavs[{i}]")
+        if w.ndim not in (1, 2) or w.device != chunks[0].device:
+            raise ValueError(f"w2vbert_fbank: wavs[{i}] must be [n] or [n, channels] on one device, got {tuple(w.shape)} on {w.device}")
+    channels = {1 if w.ndim == 1 else int(w.shape[1]) for w in chunks}
+    if len(channels) != 1 or min(channels) < 1:
+        raise ValueError(f"w2vbert_fbank: chunks of one call share a channel count >= 1, got {sorted(channels)}")
+    lengths = [(fbank_frame_count(int(w.shape[0])) + 1) // 2 for w in chunks]
+    B, device = len(chunks), chunks[0].device
+    window, mel = _fbank_tables(device)
+    n = (C.c_int64 * B)(*[int(w.shape[0]) for w in chunks])
+    ptrs = (C.c_void_p * B)(*[w.data_ptr() for w in chunks])
+    got = (C.c_int32 * B)()
+    out = torch.empty(B, max(lengths), FBANK_STRIDE * FBANK_MEL, dtype=torch.float32, device=device)
+    ws = workspace(lib().tribe_fbank_workspace_bytes(n, B), device, tag="fbank")
+    check(lib().tribe_fbank_fwd(ptrs, n, B, channels.pop(), int(bool(zscore)), window.data_ptr(), mel.data_ptr(), out.data_ptr(), out.shape[1],
+                                got, ws.data_ptr(), ws.numel(), _stream()), "tribe_fbank_fwd")
+    assert list(got) == lengths
+    return out, lengths

@@ -580,6 +580,22 @@ int tribe_word_bag_fwd(const float* table, int64_t n_words, int64_t C, const int
 int tribe_word_bag_f32_fwd(const float* table, int64_t n_words, int64_t C, const int32_t* row_ptr, const int32_t* word_idx,
                            int64_t rows, float* out, void* stream);
 
+/* ---- audio front end: 16 kHz waveform -> Wav2Vec-BERT input_features (data_utils/features/audio.py:123-127, 224-234) ----
+ * Replaces `_preprocess_wav` (mean over channels, z-score over the chunk with torch's std; only when zscore != 0) and
+ * transformers' SeamlessM4TFeatureExtractor at its defaults: * 2^15; frames of 400 samples every 160, F = 1 + (n - 400) / 160;
+ * per frame DC removal, pre-emphasis 0.97, `window` f32 [400] (Povey), 512-point one-sided DFT, power; `mel` f32 [257, 80];
+ * max(., FLT_EPSILON); log; per mel bin over the chunk's F frames (x - mean) / sqrt(var(ddof = 1) + 1e-7); one zero frame
+ * appended when F is odd; pairs of frames stacked: T = ceil(F / 2) rows of 160.
+ * wavs_host: B device pointers in a HOST array, chunk b f32 [n_host[b], channels] sample-major; n_host[b] >= 400 (else < 0).
+ * out f32 [B, T_max, 160], T_max >= every chunk's T, rows past a chunk's own T zero; lengths_host (optional) int32 [B]
+ * receives every T.  At most TRIBE_FBANK_MAX_CHUNKS chunks per call, all in one launch sequence; a chunk's rows do not
+ * depend on the rest of the batch, bit for bit.  tribe_fbank_workspace_bytes returns 0 for arguments the forward refuses. */
+#define TRIBE_FBANK_MAX_CHUNKS 32
+size_t tribe_fbank_workspace_bytes(const int64_t* n_host, int32_t B);
+int tribe_fbank_fwd(const float* const* wavs_host, const int64_t* n_host, int32_t B, int32_t channels, int32_t zscore,
+                    const float* window, const float* mel, float* out, int64_t T_max, int32_t* lengths_host, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ---- steps after the model ------------------------------------------------------------ */
 /* out[z, c, r] = in[z, r, c], f32: predictions [B, V, T'] -> [B, T', V] rows for the submission writer
  * (`pred = y_pred[i].cpu().numpy().T`, algonauts2025/callbacks.py:63-64), one launch + one D2H copy per batch. */
