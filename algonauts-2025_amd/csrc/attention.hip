@@ -24,6 +24,7 @@
 // the LDS read rate (256 B/clk/CU) is the co-bound.
 #include "attn_common.h"
 #include "attn_acc_regs.h"
+#include "host_plan.h"
 
 namespace {
 
@@ -1037,13 +1038,11 @@ int tribe_internal_attention_rotates_q(int dim_head) { return dim_head == 384 &&
 
 static tribe_attention_desc fused_desc(const uint16_t* qkv, int64_t B, int64_t T, int heads, int dim_head, float scale, uint16_t* out) {
   const int64_t inner = (int64_t)heads * dim_head;
-  tribe_attention_desc d;
+  tribe_attention_desc d = attn_zero();
   d.q = qkv; d.k = qkv + inner; d.v = qkv + 2 * inner;
   d.ld_q = d.ld_k = d.ld_v = 3 * inner;
   d.out = out; d.ld_out = inner;
-  d.B = B; d.T = T; d.heads_q = heads; d.heads_kv = heads; d.dim_head = dim_head; d.causal = 0; d.scale = scale;
-  d.rel_qe = nullptr; d.ld_rel_qe = 0; d.rel_stride_h = 0; d.rel_left = d.rel_right = 0;
-  d.lse = nullptr;
+  d.B = B; d.T = T; d.heads_q = heads; d.heads_kv = heads; d.dim_head = dim_head; d.scale = scale;
   return d;
 }
 

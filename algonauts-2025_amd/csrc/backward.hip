@@ -479,13 +479,6 @@ __global__ __launch_bounds__(256) void infonce_dlogits_kernel(const float* __res
   }
 }
 
-inline unsigned grid_for(int64_t total, int block) {
-  int64_t b = (total + block - 1) / block;
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 
 // ---- Adam over a whole parameter group in ONE launch (torch.optim.Adam semantics, defaults.py:126-133) -----------------
 // table[i] = {p, g, m, v, n}; work is cut into chunks of ADAM_CHUNK elements: chunk c belongs to tensor chunk_tensor[c] and

@@ -41,6 +41,16 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+__device__ __forceinline__ double block_sum_d(double v, double* sh) {   // sh: one slot per wave
+  v = wave_sum_d(v);
+  const int w = threadIdx.x >> 6;
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh[w] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
+  return t;
+}
 // Centred sum of squares S2 - S1^2 / n of n samples from one-pass f64 sums (Pearson statistics).  Each of the up to n adds behind
 // S1 and S2 may be off by an ulp of its running sum, so a result at or below n * DBL_EPSILON * S2 cannot be told from 0 and is 0:
 // a constant column of ~1e5 samples otherwise leaves rounding noise of either sign here, and r = noise / noise.
@@ -80,3 +90,12 @@ int tribe_internal_prof_before(int role, double flops, hipStream_t s);
 void tribe_internal_prof_after(int slot, hipStream_t s);
 
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+// grid of a 1-D launch of `total` work items: ceil(total / block), at least 1, capped at max_blocks (the default for the
+// memory-bound kernels that stride over the rest)
+static inline unsigned grid_for(int64_t total, int block, int64_t max_blocks = 256 * 8) {
+  int64_t b = (total + block - 1) / block;
+  if (b > max_blocks) b = max_blocks;
+  if (b < 1) b = 1;
+  return (unsigned)b;
+}

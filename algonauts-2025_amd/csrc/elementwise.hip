@@ -713,13 +713,6 @@ __global__ void fill_embed_kernel(float* __restrict__ x, int64_t BT, int64_t T, 
   }
 }
 
-inline unsigned grid_for(int64_t total, int block) {
-  int64_t b = (total + block - 1) / block;
-  if (b > 256 * 8) b = 256 * 8;  // cap and grid-stride (guide: memory-bound grid sizing)
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 }  // namespace
 
 extern "C" int tribe_pack_weight_bf16(const float* src, int64_t rows, int64_t cols, int64_t ld_src, uint16_t* dst,

@@ -1,9 +1,7 @@
 // Op-level entry points of the TRIBE encode path: each lowers one reference
 // function to launches of the MFMA GEMM (gemm.hip) and the streaming kernels
 // (elementwise.hip) on the caller's stream.  Host code only; no allocation, no sync.
-#include <string.h>
-
-#include "common.h"
+#include "host_plan.h"
 
 int tribe_internal_softmax(const float* S, int64_t R, int64_t T, int64_t ld_s, uint16_t* P, int64_t T_pad, int64_t ld_p,
                            hipStream_t stream);
@@ -29,36 +27,27 @@ extern "C" int tribe_attention_set_mode(int32_t mode) {
 
 namespace {
 
-inline tribe_gemm_desc gemm_zero() {
-  tribe_gemm_desc d;
-  memset(&d, 0, sizeof(d));
-  d.batch1 = d.batch0 = 1;
-  d.alpha = 1.0f;
-  d.c_dtype = TRIBE_F32;
-  return d;
-}
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // attention is processed in batch chunks so that the f32 score block stays near the Infinity Cache size
 constexpr size_t ATTN_SCORE_BUDGET = 192ull << 20;
 
-struct AttnPlan {
+struct AttnLayout {
   int64_t T_pad, chunk;
-  size_t s_bytes, p_bytes, vt_bytes;
+  float* S;       // [chunk, heads, T, T_pad] scores
+  uint16_t* P;    // the same shape, softmax rounded to bf16
+  uint16_t* Vt;   // [chunk, heads, dim_head, T_pad]
 };
 
-inline AttnPlan attn_plan(int64_t B, int64_t T, int heads, int dim_head) {
-  AttnPlan p;
+inline AttnLayout layout(int64_t B, int64_t T, int heads, int dim_head, Arena& ws) {
+  AttnLayout p;
   p.T_pad = round_up(T, 64);
   const size_t per_b = (size_t)heads * T * p.T_pad * sizeof(float);
   int64_t chunk = (int64_t)(ATTN_SCORE_BUDGET / per_b);
   if (chunk < 1) chunk = 1;
   if (chunk > B) chunk = B;
   p.chunk = chunk;
-  p.s_bytes = align256((size_t)chunk * per_b);
-  p.p_bytes = align256((size_t)chunk * heads * T * p.T_pad * 2);
-  p.vt_bytes = align256((size_t)chunk * heads * dim_head * p.T_pad * 2);
+  p.S = ws.take<float>((size_t)chunk * per_b);
+  p.P = ws.take<uint16_t>((size_t)chunk * heads * T * p.T_pad * 2);
+  p.Vt = ws.take<uint16_t>((size_t)chunk * heads * dim_head * p.T_pad * 2);
   return p;
 }
 
@@ -73,23 +62,19 @@ extern "C" int tribe_projector_fwd(const uint16_t* feat_packed, int64_t BT, int6
   TRIBE_REQUIRE(N_out > 0 && col0 >= 0 && col0 + N_out <= hidden, "tribe_projector_fwd: column slice [%lld, %lld) outside hidden=%lld",
                 (long long)col0, (long long)(col0 + N_out), (long long)hidden);
   TRIBE_REQUIRE(!subj_embed || subject_id, "tribe_projector_fwd: subject_embed without subject_id");
-  tribe_gemm_desc d = gemm_zero();
-  d.M = BT; d.N = N_out; d.K = K_pad;
-  d.A = feat_packed; d.lda = K_pad;
-  d.B = w_packed; d.ldb = K_pad;
-  d.C = x + col0; d.ldc = hidden; d.c_dtype = TRIBE_F32;
-  if (bias) { d.bias = bias; d.bias_mode = TRIBE_BIAS_COL; }
-  if (accumulate) { d.res = x + col0; d.ldres = hidden; }
+  Linear d(TRIBE_ROLE_PROJECTOR, BT, feat_packed, K_pad, w_packed, bias, x + col0, N_out, TRIBE_F32);
+  d.ldc = hidden;   // a column slice of the fused stream
+  if (accumulate) d.residual(x + col0);
   if (pos_embed) { d.rowadd = pos_embed + col0; d.ld_rowadd = hidden; d.rowadd_period = T; }
   if (subj_embed) { d.gadd = subj_embed + col0; d.gadd_index = subject_id; d.gadd_div = T; d.ld_gadd = hidden; }
-  d.role = TRIBE_ROLE_PROJECTOR;
   return tribe_gemm_bf16(&d, stream);
 }
 
 extern "C" size_t tribe_attention_workspace_bytes(int64_t B, int64_t T, int32_t heads, int32_t dim_head) {
   if (B <= 0 || T <= 0 || heads <= 0 || dim_head <= 0) return 0;
-  const AttnPlan p = attn_plan(B, T, heads, dim_head);
-  return p.s_bytes + p.p_bytes + p.vt_bytes;
+  Arena ws;
+  layout(B, T, heads, dim_head, ws);
+  return ws.off;
 }
 
 extern "C" int tribe_attention_fwd(const uint16_t* qkv, int64_t B, int64_t T, int32_t heads, int32_t dim_head, float scale,
@@ -97,39 +82,37 @@ extern "C" int tribe_attention_fwd(const uint16_t* qkv, int64_t B, int64_t T, in
   TRIBE_REQUIRE(qkv && out && workspace, "tribe_attention_fwd: null pointer");
   TRIBE_REQUIRE(B > 0 && T > 0 && heads > 0 && dim_head > 0, "tribe_attention_fwd: bad shape");
   TRIBE_REQUIRE(dim_head % 64 == 0, "tribe_attention_fwd: dim_head=%d must be a multiple of 64", dim_head);
-  TRIBE_REQUIRE(workspace_bytes >= tribe_attention_workspace_bytes(B, T, heads, dim_head), "tribe_attention_fwd: workspace too small");
+  Arena ws(workspace);
+  const AttnLayout p = layout(B, T, heads, dim_head, ws);
+  TRIBE_REQUIRE(workspace_bytes >= ws.off, "tribe_attention_fwd: workspace too small");
   TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "tribe_attention_fwd: workspace must be 256-byte aligned");
   if (g_attn_mode == 0 && tribe_internal_attention_fused_supported(dim_head))
     return tribe_internal_attention_fused(qkv, B, T, heads, dim_head, scale, out, (hipStream_t)stream);
-  const AttnPlan p = attn_plan(B, T, heads, dim_head);
   const int64_t inner = (int64_t)heads * dim_head, Tp = p.T_pad;
-  float* S = (float*)workspace;
-  uint16_t* P = (uint16_t*)((char*)workspace + p.s_bytes);
-  uint16_t* Vt = (uint16_t*)((char*)workspace + p.s_bytes + p.p_bytes);
   hipStream_t s = (hipStream_t)stream;
   for (int64_t b0 = 0; b0 < B; b0 += p.chunk) {
     const int64_t nb = (B - b0 < p.chunk) ? B - b0 : p.chunk;
     const uint16_t* q = qkv + b0 * T * 3 * inner;
-    int rc = tribe_internal_transpose_v(q, nb, T, heads, dim_head, Vt, Tp, s);
+    int rc = tribe_internal_transpose_v(q, nb, T, heads, dim_head, p.Vt, Tp, s);
     if (rc) return rc;
-    // S[b,h] = scale * Q K^T
+    // S[b,h] = scale * Q K^T  (strided views of the fused rows, batched over (b, h): not a Linear)
     tribe_gemm_desc d = gemm_zero();
     d.M = T; d.N = T; d.K = dim_head; d.batch1 = nb; d.batch0 = heads;
     d.A = q; d.lda = 3 * inner; d.sA1 = T * 3 * inner; d.sA0 = dim_head;
     d.B = q + inner; d.ldb = 3 * inner; d.sB1 = T * 3 * inner; d.sB0 = dim_head;
-    d.C = S; d.ldc = Tp; d.sC1 = (int64_t)heads * T * Tp; d.sC0 = T * Tp; d.c_dtype = TRIBE_F32;
+    d.C = p.S; d.ldc = Tp; d.sC1 = (int64_t)heads * T * Tp; d.sC0 = T * Tp; d.c_dtype = TRIBE_F32;
     d.alpha = scale;
     d.role = TRIBE_ROLE_ATTN_SCORES;
     rc = tribe_gemm_bf16(&d, stream);
     if (rc) return rc;
     // softmax in f32 (x_transformers Attend: softmax(dtype=float32)), P rounded to bf16 for the second MFMA product
-    rc = tribe_internal_softmax(S, nb * heads * T, T, Tp, P, Tp, Tp, s);
+    rc = tribe_internal_softmax(p.S, nb * heads * T, T, Tp, p.P, Tp, Tp, s);
     if (rc) return rc;
     // O[b,h] = P V   (B operand = V^T, K = T_pad zero padded on both sides)
     d = gemm_zero();
     d.M = T; d.N = dim_head; d.K = Tp; d.batch1 = nb; d.batch0 = heads;
-    d.A = P; d.lda = Tp; d.sA1 = (int64_t)heads * T * Tp; d.sA0 = T * Tp;
-    d.B = Vt; d.ldb = Tp; d.sB1 = (int64_t)heads * dim_head * Tp; d.sB0 = (int64_t)dim_head * Tp;
+    d.A = p.P; d.lda = Tp; d.sA1 = (int64_t)heads * T * Tp; d.sA0 = T * Tp;
+    d.B = p.Vt; d.ldb = Tp; d.sB1 = (int64_t)heads * dim_head * Tp; d.sB0 = (int64_t)dim_head * Tp;
     d.C = out + b0 * T * inner; d.ldc = inner; d.sC1 = T * inner; d.sC0 = dim_head; d.c_dtype = TRIBE_BF16;
     d.role = TRIBE_ROLE_ATTN_PV;
     rc = tribe_gemm_bf16(&d, stream);
@@ -139,25 +122,36 @@ extern "C" int tribe_attention_fwd(const uint16_t* qkv, int64_t B, int64_t T, in
 }
 
 namespace {
-struct EncPlan {
+struct EncLayout {
   int64_t M, inner;
-  size_t xn_bytes, big_bytes, attn_bytes, norm_bytes, split_bytes;
-  bool fuse_norm;   // ScaleNorm folded into the GEMMs either side of it (needs whole 256-column tiles)
+  bool fuse_norm;      // ScaleNorm folded into the GEMMs either side of it (needs whole 256-column tiles)
+  uint16_t* xn;        // [M, dim] bf16 input of QKV / FF1
+  uint16_t* qkv;       // [M, 3*inner]
+  uint16_t* ao;        // [M, inner], behind qkv
+  uint16_t* hbuf;      // [M, ff_inner], over qkv | ao (dead by then)
+  void* attn_ws; size_t attn_bytes;
+  float* ssq;          // [M, n_part] partial sums of squares (<= dim / 32 slots per row, by the producer's tile)
+  float* rowf;         // [M] ScaleNorm factors, behind ssq
+  void* split_ws; size_t split_bytes;
 };
-inline EncPlan enc_plan(const tribe_encoder_desc* d) {
-  EncPlan p;
-  p.M = d->B * d->T;
-  p.inner = (int64_t)d->heads * d->dim_head;
-  p.xn_bytes = align256((size_t)p.M * d->dim * 2);
-  const int64_t wide = (4 * p.inner > d->ff_inner) ? 4 * p.inner : d->ff_inner;  // qkv | attn_out  aliases  ff hidden
-  p.big_bytes = align256((size_t)p.M * wide * 2);
-  p.attn_bytes = align256(tribe_attention_workspace_bytes(d->B, d->T, d->heads, d->dim_head));
-  p.fuse_norm = d->dim % 256 == 0 && p.inner % 256 == 0 && d->ff_inner % 256 == 0;
-  p.norm_bytes = p.fuse_norm ? align256((size_t)p.M * (d->dim / 32 + 1) * 4) : 0;   // partial sums of squares (<= dim / 32 slots per row, by the producer's tile) + the row factors
+inline EncLayout layout(const tribe_encoder_desc* d, Arena& ws) {
+  EncLayout p;
+  const int64_t M = p.M = d->B * d->T;
+  const int64_t inner = p.inner = (int64_t)d->heads * d->dim_head;
+  p.xn = ws.take<uint16_t>((size_t)M * d->dim * 2);
+  const int64_t wide = (4 * inner > d->ff_inner) ? 4 * inner : d->ff_inner;
+  p.qkv = p.hbuf = ws.take<uint16_t>((size_t)M * wide * 2);
+  p.ao = p.qkv + (size_t)M * 3 * inner;
+  p.attn_bytes = tribe_attention_workspace_bytes(d->B, d->T, d->heads, d->dim_head);
+  p.attn_ws = ws.take<void>(p.attn_bytes);
+  p.fuse_norm = d->dim % 256 == 0 && inner % 256 == 0 && d->ff_inner % 256 == 0;
+  p.ssq = p.fuse_norm ? ws.take<float>((size_t)M * (d->dim / 32 + 1) * 4) : nullptr;
+  p.rowf = p.fuse_norm ? p.ssq + (size_t)M * (d->dim / 32) : nullptr;
   // few rows (BASELINE config 1: M = 128): the four GEMMs of a layer are well under one round of tiles and run split over K
   // (tribe_gemm_desc.stream_k) -- up to 8 f32 shares of the widest output
-  const int64_t widest = 3 * p.inner > d->ff_inner ? (3 * p.inner > d->dim ? 3 * p.inner : d->dim) : (d->ff_inner > d->dim ? d->ff_inner : d->dim);
-  p.split_bytes = p.M <= 512 ? align256((size_t)8 * p.M * widest * 4) : 0;
+  const int64_t widest = 3 * inner > d->ff_inner ? (3 * inner > d->dim ? 3 * inner : d->dim) : (d->ff_inner > d->dim ? d->ff_inner : d->dim);
+  p.split_bytes = M <= 512 ? align256((size_t)8 * M * widest * 4) : 0;
+  p.split_ws = p.split_bytes ? ws.take<void>(p.split_bytes) : nullptr;
   return p;
 }
 inline int enc_validate(const tribe_encoder_desc* d) {
@@ -175,8 +169,9 @@ inline int enc_validate(const tribe_encoder_desc* d) {
 
 extern "C" size_t tribe_encoder_workspace_bytes(const tribe_encoder_desc* d) {
   if (!d || d->B <= 0 || d->T <= 0) return 0;
-  const EncPlan p = enc_plan(d);
-  return p.xn_bytes + p.big_bytes + p.attn_bytes + p.norm_bytes + p.split_bytes;
+  Arena ws;
+  layout(d, ws);
+  return ws.off;
 }
 
 extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, void* workspace,
@@ -185,25 +180,18 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
   if (rc) return rc;
   TRIBE_REQUIRE(x && y && workspace, "tribe_encoder_fwd: null pointer");
   TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "tribe_encoder_fwd: workspace must be 256-byte aligned");
-  TRIBE_REQUIRE(workspace_bytes >= tribe_encoder_workspace_bytes(d), "tribe_encoder_fwd: workspace too small (%zu < %zu)",
-                workspace_bytes, tribe_encoder_workspace_bytes(d));
-  const EncPlan p = enc_plan(d);
+  Arena ws(workspace);
+  const EncLayout p = layout(d, ws);
+  TRIBE_REQUIRE(workspace_bytes >= ws.off, "tribe_encoder_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
   const int64_t M = p.M, inner = p.inner, dim = d->dim;
-  uint16_t* xn = (uint16_t*)workspace;
-  uint16_t* big = (uint16_t*)((char*)workspace + p.xn_bytes);
-  uint16_t* qkv = big;                         // [M, 3*inner]
-  uint16_t* ao = big + (size_t)M * 3 * inner;  // [M, inner]
-  uint16_t* hbuf = big;                        // [M, ff_inner]  (qkv/ao are dead by then)
-  void* attn_ws = (char*)workspace + p.xn_bytes + p.big_bytes;
-  float* ssq = (float*)((char*)workspace + p.xn_bytes + p.big_bytes + p.attn_bytes);   // [M, n_part] partial sums of squares
-  float* rowf = ssq + (size_t)M * (dim / 32);                                          // [M] ScaleNorm factors
-  void* split_ws = (char*)workspace + p.xn_bytes + p.big_bytes + p.attn_bytes + p.norm_bytes;
+  uint16_t *xn = p.xn, *qkv = p.qkv, *ao = p.ao, *hbuf = p.hbuf;
+  float *ssq = p.ssq, *rowf = p.rowf;
   // a GEMM of a small batch may run split over K: hand it the workspace when the launcher says it would use one
   auto allow_split = [&](tribe_gemm_desc& g) {
     if (p.split_bytes == 0) return;
     g.stream_k = 1;
     const int64_t need = tribe_gemm_stream_k_workspace_bytes(&g);
-    if (need > 0 && (size_t)need <= p.split_bytes) { g.stream_k_ws = split_ws; g.stream_k_ws_bytes = (int64_t)p.split_bytes; }
+    if (need > 0 && (size_t)need <= p.split_bytes) { g.stream_k_ws = p.split_ws; g.stream_k_ws_bytes = (int64_t)p.split_bytes; }
     else g.stream_k = 0;
   };
   int64_t n_part = dim / 64;   // slots per row the LAST producer wrote (one per wave column group of its tile: tribe_gemm_sumsq_slots)
@@ -220,18 +208,11 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
     TRIBE_REQUIRE(L.attn_norm_g && L.w_qkv && L.w_out && L.ff_norm_g && L.w_ff1 && L.b_ff1 && L.w_ff2 && L.b_ff2,
                   "tribe_encoder_fwd: layer %d has a null parameter", l);
     // ---- attention block: x = to_out(attn(rotary(qkv(norm(x))))) + x * residual_scale ----
-    tribe_gemm_desc g = gemm_zero();
-    if (have_factors) {
-      rc = tribe_rownorm_scale_fwd(ssq, M, n_part, L.attn_norm_g, d->norm_gain_scale, d->norm_eps, rowf, stream);
-      g.row_scale = rowf;
-    } else {
-      rc = tribe_scalenorm_fwd(x, M, dim, L.attn_norm_g, d->norm_gain_scale, d->norm_eps, xn, TRIBE_BF16, stream);
-    }
+    rc = have_factors ? tribe_rownorm_scale_fwd(ssq, M, n_part, L.attn_norm_g, d->norm_gain_scale, d->norm_eps, rowf, stream)
+                      : tribe_scalenorm_fwd(x, M, dim, L.attn_norm_g, d->norm_gain_scale, d->norm_eps, xn, TRIBE_BF16, stream);
     if (rc) return rc;
-    g.M = M; g.N = 3 * inner; g.K = dim;
-    g.A = xn; g.lda = dim; g.B = L.w_qkv; g.ldb = dim;
-    g.C = qkv; g.ldc = 3 * inner; g.c_dtype = TRIBE_BF16;
-    g.role = TRIBE_ROLE_QKV;
+    tribe_gemm_desc g = Linear(TRIBE_ROLE_QKV, M, xn, dim, L.w_qkv, nullptr, qkv, 3 * inner, TRIBE_BF16);
+    if (have_factors) g.row_scale = rowf;
     allow_split(g);
     rc = tribe_gemm_bf16(&g, stream);
     if (rc) return rc;
@@ -248,14 +229,10 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
     }
     rc = q_in_attn ? tribe_internal_attention_fused_qrot(qkv, d->B, d->T, d->heads, d->dim_head, scale, ao, d->cos_tab, d->sin_tab,
                                                          d->rot_dim, (hipStream_t)stream)
-                   : tribe_attention_fwd(qkv, d->B, d->T, d->heads, d->dim_head, scale, ao, attn_ws, p.attn_bytes, stream);
+                   : tribe_attention_fwd(qkv, d->B, d->T, d->heads, d->dim_head, scale, ao, p.attn_ws, p.attn_bytes, stream);
     if (rc) return rc;
-    g = gemm_zero();
-    g.M = M; g.N = dim; g.K = inner;
-    g.A = ao; g.lda = inner; g.B = L.w_out; g.ldb = inner;
-    g.C = x; g.ldc = dim; g.c_dtype = TRIBE_F32;
-    g.res = x; g.ldres = dim; g.res_scale = L.attn_res_scale;
-    g.role = TRIBE_ROLE_OUT_PROJ;
+    g = Linear(TRIBE_ROLE_OUT_PROJ, M, ao, inner, L.w_out, nullptr, x, dim, TRIBE_F32).residual(x);
+    g.res_scale = L.attn_res_scale;
     if (fuse) {
       g.c_bf16 = xn; g.ld_c_bf16 = dim; g.row_sumsq = ssq;
       n_part = tribe_gemm_sumsq_slots(&g);
@@ -266,29 +243,16 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
     rc = tribe_gemm_bf16(&g, stream);
     if (rc) return rc;
     // ---- feed-forward block: x = W2 gelu(W1 norm(x) + b1) + b2 + x * residual_scale ----
-    g = gemm_zero();
-    if (fuse) {
-      rc = tribe_rownorm_scale_fwd(ssq, M, n_part, L.ff_norm_g, d->norm_gain_scale, d->norm_eps, rowf, stream);
-      g.row_scale = rowf;
-    } else {
-      rc = tribe_scalenorm_fwd(x, M, dim, L.ff_norm_g, d->norm_gain_scale, d->norm_eps, xn, TRIBE_BF16, stream);
-    }
+    rc = fuse ? tribe_rownorm_scale_fwd(ssq, M, n_part, L.ff_norm_g, d->norm_gain_scale, d->norm_eps, rowf, stream)
+              : tribe_scalenorm_fwd(x, M, dim, L.ff_norm_g, d->norm_gain_scale, d->norm_eps, xn, TRIBE_BF16, stream);
     if (rc) return rc;
-    g.M = M; g.N = d->ff_inner; g.K = dim;
-    g.A = xn; g.lda = dim; g.B = L.w_ff1; g.ldb = dim;
-    g.C = hbuf; g.ldc = d->ff_inner; g.c_dtype = TRIBE_BF16;
-    g.bias = L.b_ff1; g.bias_mode = TRIBE_BIAS_COL; g.act = TRIBE_ACT_GELU;
-    g.role = TRIBE_ROLE_FF1;
+    g = Linear(TRIBE_ROLE_FF1, M, xn, dim, L.w_ff1, L.b_ff1, hbuf, d->ff_inner, TRIBE_BF16).activation(TRIBE_ACT_GELU);
+    if (fuse) g.row_scale = rowf;
     allow_split(g);
     rc = tribe_gemm_bf16(&g, stream);
     if (rc) return rc;
-    g = gemm_zero();
-    g.M = M; g.N = dim; g.K = d->ff_inner;
-    g.A = hbuf; g.lda = d->ff_inner; g.B = L.w_ff2; g.ldb = d->ff_inner;
-    g.C = x; g.ldc = dim; g.c_dtype = TRIBE_F32;
-    g.bias = L.b_ff2; g.bias_mode = TRIBE_BIAS_COL;
-    g.res = x; g.ldres = dim; g.res_scale = L.ff_res_scale;
-    g.role = TRIBE_ROLE_FF2;
+    g = Linear(TRIBE_ROLE_FF2, M, hbuf, d->ff_inner, L.w_ff2, L.b_ff2, x, dim, TRIBE_F32).residual(x);
+    g.res_scale = L.ff_res_scale;
     have_factors = fuse && l + 1 < d->depth;   // the next layer's QKV takes the raw bf16(x) + factors
     if (have_factors) {
       g.c_bf16 = xn; g.ld_c_bf16 = dim; g.row_sumsq = ssq;
@@ -310,12 +274,10 @@ extern "C" int tribe_voxel_head_fwd(const uint16_t* x, int64_t B, int64_t T, int
   // y[b] (V x T) = W_s^T (V x C) . x_b^T (C x T): the T-contiguous output needs no transposed store,
   // and the per-subject weight is selected by the gather index instead of being materialised per sample
   // (the reference's index_select copies B x 12.3 MB, common.py:61).
-  tribe_gemm_desc d = gemm_zero();
-  d.M = V; d.N = T; d.K = C_pad; d.batch1 = B;
-  d.A = w_packed; d.lda = C_pad; d.sA1 = V_pad * C_pad; d.gather1 = subjects; d.gather_a = 1;
-  d.B = x; d.ldb = C_pad; d.sB1 = T * C_pad;
-  d.C = y; d.ldc = T; d.sC1 = V * T; d.c_dtype = TRIBE_F32;
+  // the "input" of this Linear is the weight (rows = voxels, one bias per row) and its "weight" is x_b
+  Linear d(TRIBE_ROLE_VOXEL_HEAD, V, w_packed, C_pad, x, nullptr, y, T, TRIBE_F32);
+  d.batch1 = B; d.sA1 = V_pad * C_pad; d.gather1 = subjects; d.gather_a = 1;
+  d.sB1 = T * C_pad; d.sC1 = V * T;
   if (bias) { d.bias = bias; d.bias_mode = TRIBE_BIAS_ROW; d.gather_bias = 1; d.sBias1 = V; }
-  d.role = TRIBE_ROLE_VOXEL_HEAD;
   return tribe_gemm_bf16(&d, stream);
 }

@@ -263,11 +263,7 @@ __global__ void corr_finalize_kernel(const double* __restrict__ cov, int64_t N, 
   corr[p] = cov[p] / sqrt(cov[i * N + i] * cov[j * N + j]);
 }
 
-inline unsigned grid_1d(int64_t total, int block) {
-  int64_t g = (total + block - 1) / block;
-  if (g > 65536 * 16) g = 65536 * 16;
-  return (unsigned)(g < 1 ? 1 : g);
-}
+constexpr int64_t GRID_CAP = 65536 * 16;   // grid_for: these kernels take one work item per lane up to here
 
 }  // namespace
 
@@ -279,10 +275,10 @@ extern "C" int tribe_group_mean_fwd(const float* states, int64_t batch, int64_t 
   hipStream_t s = (hipStream_t)stream;
   const bool vec = plane % 4 == 0 && ((uintptr_t)states % 16) == 0 && ((uintptr_t)out % 16) == 0;
   if (vec)
-    hipLaunchKernelGGL(group_mean_kernel<4>, dim3(grid_1d(batch * n_groups * (plane / 4), 256)), dim3(256), 0, s, states, batch, n_states,
+    hipLaunchKernelGGL(group_mean_kernel<4>, dim3(grid_for(batch * n_groups * (plane / 4), 256, GRID_CAP)), dim3(256), 0, s, states, batch, n_states,
                        plane, lo, hi, n_groups, out);
   else
-    hipLaunchKernelGGL(group_mean_kernel<1>, dim3(grid_1d(batch * n_groups * plane, 256)), dim3(256), 0, s, states, batch, n_states, plane,
+    hipLaunchKernelGGL(group_mean_kernel<1>, dim3(grid_for(batch * n_groups * plane, 256, GRID_CAP)), dim3(256), 0, s, states, batch, n_states, plane,
                        lo, hi, n_groups, out);
   TRIBE_LAUNCH_CHECK();
   return 0;
@@ -360,9 +356,9 @@ extern "C" int tribe_weighted_sum_fwd(const float* preds, int64_t N, int64_t M, 
   TRIBE_REQUIRE(N > 0 && M > 0 && V > 0 && M % V == 0, "tribe_weighted_sum_fwd: bad shape N=%lld M=%lld V=%lld", (long long)N, (long long)M, (long long)V);
   hipStream_t s = (hipStream_t)stream;
   if (w_column)
-    hipLaunchKernelGGL(weighted_sum_kernel<1>, dim3(grid_1d(M, 256)), dim3(256), 0, s, preds, N, M, V, w_column, w_set, out);
+    hipLaunchKernelGGL(weighted_sum_kernel<1>, dim3(grid_for(M, 256, GRID_CAP)), dim3(256), 0, s, preds, N, M, V, w_column, w_set, out);
   else
-    hipLaunchKernelGGL(weighted_sum_kernel<0>, dim3(grid_1d(M, 256)), dim3(256), 0, s, preds, N, M, V, w_column, w_set, out);
+    hipLaunchKernelGGL(weighted_sum_kernel<0>, dim3(grid_for(M, 256, GRID_CAP)), dim3(256), 0, s, preds, N, M, V, w_column, w_set, out);
   TRIBE_LAUNCH_CHECK();
   return 0;
 }

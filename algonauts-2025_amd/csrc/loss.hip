@@ -9,17 +9,6 @@
 
 namespace {
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-  return t;
-}
-
 // HBM-bound: 8 bytes read per element.  Four independent float4 pairs are requested before any is consumed (128 B in
 // flight per lane; 2048 workgroups x 256 lanes cover the ~16 MB the chip needs in flight at 8 TB/s), f32 partial sums of
 // at most 16 squared differences are folded into an f64 carry.

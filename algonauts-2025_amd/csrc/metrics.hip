@@ -26,17 +26,6 @@ constexpr int RPAD = RQ + 4;
 
 __device__ __forceinline__ float inv_norm(float nrm) { return 1.0f / (1e-15f + nrm); }
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {   // sh: one slot per wave
-  v = wave_sum_d(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-  return t;
-}
-
 // ---- prep ------------------------------------------------------------------------------------------------------------------
 // grid (N, n_tensors), 1024 lanes.  Fast path (T' contiguous, 16-byte aligned rows, T % 4 == 0): sixteen lanes own one (n, v) row
 // of T floats (float4 per lane) and each group keeps four rows' loads in flight (256 rows per workgroup); strided fallback: one lane

@@ -22,17 +22,6 @@ constexpr int FWD_MAX_WG = 2048;   // tribe_elem_loss_workspace_bytes: one f64 p
 constexpr int FWD_UNROLL = 4;      // float4 pairs requested before the first is consumed
 constexpr int BWD_MAX_WG = 4096;
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[w] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-  return t;
-}
-
 // the comparisons (not fminf / fmaxf) keep a NaN difference a NaN, as torch does
 template <int KIND>
 __device__ __forceinline__ float loss_value(float p, float t, float c) {

@@ -151,6 +151,141 @@ def test_split_planner_leaves_the_headline_shapes_whole():
     assert nbytes(9216, 3072, 16384, trans_ab=1) == 0 and nbytes(3072, 3072, 16384, trans_ab=1) == 0
 
 
+def _planner_cases():
+    """(name, planner, arguments) of every workspace planner at the shapes test_workspace_totals_are_pinned pins.  The fp8_host arrays the
+    planners only test for NULL are kept alive by the descriptors that point at them."""
+    from tribe_hip import _lib
+
+    def enc(B, T, dim, heads, dim_head, ff):
+        d = _lib.EncoderDesc()
+        d.B, d.T, d.dim, d.depth, d.heads, d.dim_head, d.ff_inner = B, T, dim, 8, heads, dim_head, ff
+        return d
+
+    def llama(B, fp8):
+        d = _lib.LlamaDesc()
+        d.B, d.T, d.dim, d.depth, d.heads_q, d.heads_kv, d.dim_head, d.inter = B, 1024, 3072, 28, 24, 8, 128, 8192
+        if fp8:
+            d.fp8_host = (_lib.LlamaFp8Layer * 1)()
+        return d
+
+    def vit(B, dim, mlp, fp8):   # 8 x 4 x 4 = 128 tokens per clip
+        d = _lib.Vjepa2Desc()
+        d.B, d.frames, d.chans, d.height, d.width, d.tubelet, d.patch = B, 16, 3, 64, 64, 2, 16
+        d.dim, d.depth, d.heads, d.dim_head, d.mlp, d.K_pad = dim, 2, dim // 64, 64, mlp, 1536
+        if fp8:
+            d.fp8_host = (_lib.VitFp8Layer * 1)()
+        return d
+
+    def w2v(B, fp8):
+        d = _lib.W2vBertDesc()
+        d.B, d.T, d.feat_dim, d.feat_pad, d.dim, d.depth, d.heads, d.dim_head, d.inter = B, 3000, 160, 192, 1024, 24, 16, 64, 4096
+        d.conv_kernel, d.rel_left, d.rel_right, d.n_out = 31, 64, 8, 120
+        if fp8:
+            d.fp8_host = (_lib.ConformerFp8Layer * 1)()
+        return d
+
+    cases = [
+        ("encoder headline", "tribe_encoder_workspace_bytes", (enc(64, 1024, 3072, 8, 384, 12288),)),
+        ("encoder config 1 (split-K)", "tribe_encoder_workspace_bytes", (enc(1, 128, 3072, 8, 384, 12288),)),
+        ("encoder unfused norm", "tribe_encoder_workspace_bytes", (enc(2, 64, 192, 1, 192, 768),)),
+        ("encoder B=0", "tribe_encoder_workspace_bytes", (enc(0, 1024, 3072, 8, 384, 12288),)),
+        ("attention chunk < B", "tribe_attention_workspace_bytes", (64, 1024, 8, 384)),
+        ("attention chunk == B", "tribe_attention_workspace_bytes", (4, 128, 8, 384)),
+        ("attention odd T", "tribe_attention_workspace_bytes", (2, 100, 4, 64)),
+        ("attention B=0", "tribe_attention_workspace_bytes", (0, 1024, 8, 384)),
+    ]
+    for fp8 in (False, True):
+        tag = " fp8" if fp8 else ""
+        cases += [
+            ("llama 3B" + tag, "tribe_llama_workspace_bytes", (llama(8, fp8),)),
+            ("llama B=0" + tag, "tribe_llama_workspace_bytes", (llama(0, fp8),)),
+            ("vjepa2 act > col" + tag, "tribe_vjepa2_workspace_bytes", (vit(2, 1408, 6144, fp8),)),
+            ("vjepa2 col > act" + tag, "tribe_vjepa2_workspace_bytes", (vit(2, 64, 64, fp8),)),
+            ("vjepa2 B=0" + tag, "tribe_vjepa2_workspace_bytes", (vit(0, 1408, 6144, fp8),)),
+            ("w2vbert" + tag, "tribe_w2vbert_workspace_bytes", (w2v(8, fp8),)),
+            ("w2vbert B=0" + tag, "tribe_w2vbert_workspace_bytes", (w2v(0, fp8),)),
+        ]
+    return cases
+
+
+# what the library of the commit before the planners moved onto the shared arena (csrc/host_plan.h) returned for _planner_cases()
+WORKSPACE_TOTALS = {
+    "encoder headline": 2378432512,
+    "encoder config 1 (split-K)": 55886336,
+    "encoder unfused norm": 3489792,
+    "encoder B=0": 0,
+    "attention chunk < B": 339738624,
+    "attention chunk == B": 6291456,
+    "attention odd T": 745472,
+    "attention B=0": 0,
+    "llama 3B": 520093696,
+    "llama B=0": 0,
+    "vjepa2 act > col": 8192000,
+    "vjepa2 col > act": 1015808,
+    "vjepa2 B=0": 0,
+    "w2vbert": 589824000,
+    "w2vbert B=0": 0,
+    "llama 3B fp8": 587202560,
+    "llama B=0 fp8": 0,
+    "vjepa2 act > col fp8": 9764864,
+    "vjepa2 col > act fp8": 1032192,
+    "vjepa2 B=0 fp8": 0,
+    "w2vbert fp8": 688128000,
+    "w2vbert B=0 fp8": 0,
+}
+
+
+def test_workspace_totals_are_pinned():
+    """Every workspace planner returns, byte for byte, what it returned before its layout was written once for both the planner and
+    the forward; and every forward refuses a workspace one byte short of that before anything could reach the device (no GPU here)."""
+    from tribe_hip import _lib
+
+    handle = _lib.lib()
+    got = {}
+    for name, planner, args in _planner_cases():
+        got[name] = getattr(handle, planner)(*[ctypes.byref(a) if isinstance(a, ctypes.Structure) else a for a in args])
+    assert got == WORKSPACE_TOTALS
+
+    # valid descriptors with dummy (never dereferenced) data pointers, at small shapes
+    mem = ctypes.create_string_buffer(1024)
+    ptr = (ctypes.addressof(mem) + 255) // 256 * 256
+
+    def short(fwd, planner, plan_args, call):
+        need = getattr(handle, planner)(*plan_args)
+        assert need > 0
+        rc = call(need - 1)
+        assert rc < 0 and b"workspace" in handle.tribe_last_error(), (fwd, rc, handle.tribe_last_error())
+
+    e = _lib.EncoderDesc()
+    e.B, e.T, e.dim, e.depth, e.heads, e.dim_head, e.ff_inner, e.rot_dim = 2, 40, 768, 1, 4, 192, 3072, 0
+    e.norm_gain_scale, e.norm_eps, e.final_norm_g = 1.0, 1e-5, ptr
+    e.layers_host = (_lib.EncoderLayer * 1)()
+    short("tribe_encoder_fwd", "tribe_encoder_workspace_bytes", (ctypes.byref(e),),
+          lambda n: handle.tribe_encoder_fwd(ctypes.byref(e), ptr, ptr, _lib.F32, ptr, n, None))
+    short("tribe_attention_fwd", "tribe_attention_workspace_bytes", (2, 40, 4, 192),
+          lambda n: handle.tribe_attention_fwd(ptr, 2, 40, 4, 192, 1.0, ptr, ptr, n, None))
+    ll = _lib.LlamaDesc()
+    ll.B, ll.T, ll.dim, ll.depth, ll.heads_q, ll.heads_kv, ll.dim_head, ll.inter, ll.vocab = 2, 24, 256, 1, 4, 2, 64, 512, 100
+    ll.rms_eps, ll.embed, ll.embed_dtype, ll.final_norm_w, ll.cos_tab, ll.sin_tab, ll.ids = 1e-5, ptr, _lib.F32, ptr, ptr, ptr, ptr
+    ll.layers_host = (_lib.LlamaLayer * 1)()
+    short("tribe_llama_fwd", "tribe_llama_workspace_bytes", (ctypes.byref(ll),),
+          lambda n: handle.tribe_llama_fwd(ctypes.byref(ll), ptr, ptr, n, None))
+    v = _lib.Vjepa2Desc()
+    v.B, v.frames, v.chans, v.height, v.width, v.tubelet, v.patch = 2, 4, 3, 32, 32, 2, 16
+    v.dim, v.depth, v.heads, v.dim_head, v.mlp, v.K_pad, v.ln_eps = 128, 1, 2, 64, 256, 1536, 1e-6
+    v.w_patch, v.cos_tab, v.sin_tab, v.pixels = ptr, ptr, ptr, ptr
+    v.layers_host = (_lib.VitLayer * 1)()
+    short("tribe_vjepa2_fwd", "tribe_vjepa2_workspace_bytes", (ctypes.byref(v),),
+          lambda n: handle.tribe_vjepa2_fwd(ctypes.byref(v), ptr, ptr, n, None))
+    w = _lib.W2vBertDesc()
+    w.B, w.T, w.feat_dim, w.feat_pad, w.dim, w.depth, w.heads, w.dim_head, w.inter = 2, 50, 160, 192, 128, 1, 2, 64, 256
+    w.conv_kernel, w.rel_left, w.rel_right, w.ln_eps, w.n_out = 31, 64, 8, 1e-5, 5
+    w.fp_ln_w, w.fp_ln_b, w.w_fp, w.features, w.out_index = ptr, ptr, ptr, ptr, ptr
+    w.layers_host = (_lib.ConformerLayer * 1)()
+    short("tribe_w2vbert_fwd", "tribe_w2vbert_workspace_bytes", (ctypes.byref(w),),
+          lambda n: handle.tribe_w2vbert_fwd(ctypes.byref(w), ptr, ptr, n, None))
+
+
 def test_host_surface_matches_reference_names():
     from algonauts2025.model import FmriEncoder, FmriEncoderConfig
     from algonauts2025.pl_module import BrainModule
