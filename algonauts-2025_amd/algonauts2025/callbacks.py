@@ -176,7 +176,7 @@ class StochasticWeightAveraging:
             self._prepare(pl_module)
         table, owner, start = self._work
         _lib.check(_lib.lib().tribe_swa_update(table.data_ptr(), owner.data_ptr(), start.data_ptr(), owner.numel(), 1.0 / (self.n_averaged + 1),
-                                               torch.cuda.current_stream().cuda_stream), "tribe_swa_update")
+                                               ops._stream()), "tribe_swa_update")
         self.n_averaged += 1
 
     def on_train_epoch_start(self, trainer: tp.Any, pl_module: tp.Any) -> None:

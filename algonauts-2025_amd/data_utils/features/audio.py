@@ -22,9 +22,10 @@ import pydantic
 import torch
 
 from tribe_hip import ops
-from tribe_hip._lib import ConformerLayer, W2vBertDesc, check, lib
+from tribe_hip._lib import ConformerFp8Layer, ConformerLayer, W2vBertDesc
 from tribe_hip.ops import fbank_frame_count, kaldi_mel_filters, povey_window  # noqa: F401  (host helpers of the front end)
 
+from .extractor_host import ExtractorHost
 from .plugin import HbmFeaturePlugin
 
 # facebook/w2v-bert-2.0 hyper-parameters (public model card; configuration input, not verifiable offline)
@@ -40,9 +41,18 @@ def nearest_index(t_in: int, t_out: int) -> torch.Tensor:
     return torch.clamp((torch.arange(t_out, dtype=torch.float32) * scale).floor().to(torch.int64), max=t_in - 1)
 
 
-class HipWav2Vec2Bert:
+class HipWav2Vec2Bert(ExtractorHost):
+    """Packed bf16 weights of Wav2Vec2BertModel + the forward-with-resampling launcher.  enable_fp8(calibration_features
+    [B, T, feat_dim]) switches the four feed-forward Linears of every layer (70 % of a Conformer layer's GEMM flops) to e4m3; its
+    amax table columns are ffn1 in / out, ffn2 in / out."""
+
+    FORWARD, FP8_LAYER, FP8_FIELDS = "tribe_w2vbert_fwd", ConformerFp8Layer, ("w_ffn1_in", "w_ffn1_out", "w_ffn2_in", "w_ffn2_out")
+    FP8_SOURCE = "ffn_packs"
+    FP8_WIDTHS_ERROR = "fp8 path: hidden_size and intermediate_size must be multiples of 128"
+
     def __init__(self, config: tp.Any, state_dict: dict[str, torch.Tensor], device: str | torch.device = "cuda"):
-        g = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
+        super().__init__(config, state_dict, device)
+        g, f32, own = self.cfg, self.f32, self.own
         self.dim, self.depth, self.heads, self.inter = g("hidden_size"), g("num_hidden_layers"), g("num_attention_heads"), g("intermediate_size")
         self.feat_dim, self.kernel = g("feature_projection_input_dim"), g("conv_depthwise_kernel_size")
         self.left, self.right = g("left_max_position_embeddings"), g("right_max_position_embeddings")
@@ -51,24 +61,12 @@ class HipWav2Vec2Bert:
             raise NotImplementedError("only the w2v-bert-2.0 configuration (relative_key positions, swish) is built")
         self.dim_head = self.dim // self.heads
         self.feat_pad = ops.round_up(self.feat_dim, 64)
-        self.device = dev = torch.device(device)
-        sd = state_dict
-
-        def f32(name: str) -> torch.Tensor:
-            return sd[name].detach().to(device=dev, dtype=torch.float32).contiguous()
-
-        self.keep: list[torch.Tensor] = []
-
-        def own(t: torch.Tensor) -> int:
-            self.keep.append(t)
-            return t.data_ptr()
-
+        self.fp8_widths = (self.dim, self.inter)
         self.fp_ln = (f32("feature_projection.layer_norm.weight"), f32("feature_projection.layer_norm.bias"))
         self.w_fp = ops.pack_weight(f32("feature_projection.projection.weight"), cols_pad=self.feat_pad)
         self.b_fp = f32("feature_projection.projection.bias")
         self.layers = (ConformerLayer * max(self.depth, 1))()
         self.ffn_packs: list[list[torch.Tensor]] = []     # per layer: bf16 ffn1 in / out, ffn2 in / out (what enable_fp8 quantises)
-        self.fp8_layers = None
         H = self.dim
         for i in range(self.depth):
             p = f"encoder.layers.{i}."
@@ -97,34 +95,10 @@ class HipWav2Vec2Bert:
             L.dw_ln_w, L.dw_ln_b = own(f32(c + "depthwise_layer_norm.weight")), own(f32(c + "depthwise_layer_norm.bias"))
             L.w_pw2 = own(ops.pack_weight(f32(c + "pointwise_conv2.weight").squeeze(-1)))
             L.final_ln_w, L.final_ln_b = own(f32(p + "final_layer_norm.weight")), own(f32(p + "final_layer_norm.bias"))
+        del self._sd
 
-    def enable_fp8(self, calibration_features: torch.Tensor, margin: float = 1.0) -> torch.Tensor:
-        """e4m3 feed-forward GEMMs (BASELINE config 5; the four FFN Linears are 70 % of a Conformer layer's GEMM flops), as
-        HipVJEPA2Encoder.enable_fp8: per-tensor weight scales, static input scales from one bf16 pass over `calibration_features`
-        [B, T, feat_dim].  Returns the amax table f32 [depth, 4] (ffn1 in / out, ffn2 in / out)."""
-        from tribe_hip._lib import ConformerFp8Layer
-
-        if self.dim % 128 or self.inter % 128:
-            raise ValueError("fp8 path: hidden_size and intermediate_size must be multiples of 128")
-        self.fp8_layers = None
-        amax = torch.zeros(max(self.depth, 1), 4, dtype=torch.float32, device=self.device)
+    def _calibrate(self, calibration_features: torch.Tensor, amax: torch.Tensor) -> None:
         self.hidden_states_resampled(calibration_features, 1, _amax=amax)
-        table = amax.cpu()
-        if not bool((table[: self.depth] > 0).all()):
-            raise ValueError("fp8 calibration saw an all-zero GEMM input")
-        layers = (ConformerFp8Layer * max(self.depth, 1))()
-        self.fp8_packs = []
-        for i in range(self.depth):
-            q = []
-            for j, w in enumerate(self.ffn_packs[i]):
-                w_scale = float(ops.absmax(w)) / ops.FP8_MAX
-                q.append(ops.quantize_fp8(w, w_scale, K_pad=w.shape[1]))
-                layers[i].w_scale[j] = w_scale
-                layers[i].in_scale[j] = float(table[i, j]) * margin / ops.FP8_MAX
-            layers[i].w_ffn1_in, layers[i].w_ffn1_out, layers[i].w_ffn2_in, layers[i].w_ffn2_out = (t.data_ptr() for t in q)
-            self.fp8_packs.append(q)
-        self.fp8_layers = layers
-        return table
 
     def hidden_states_resampled(self, input_features: torch.Tensor, n_out: int, fp8: bool | None = None,
                                 _amax: torch.Tensor | None = None) -> torch.Tensor:
@@ -144,18 +118,8 @@ class HipWav2Vec2Bert:
         d.w_fp, d.b_fp = self.w_fp.data_ptr(), self.b_fp.data_ptr()
         d.layers_host = C.cast(self.layers, C.POINTER(ConformerLayer))
         d.features, d.out_index, d.n_out = feats.data_ptr(), idx.data_ptr(), n_out
-        use_fp8 = (self.fp8_layers is not None) if fp8 is None else fp8
-        if use_fp8 and _amax is None:
-            if self.fp8_layers is None:
-                raise ValueError("hidden_states_resampled(fp8=True) before enable_fp8()")
-            d.fp8_host = C.cast(self.fp8_layers, C.POINTER(type(self.fp8_layers[0])))
-        if _amax is not None:
-            d.amax_out = _amax.data_ptr()
         states = torch.empty(self.depth + 1, B, n_out, self.dim, dtype=torch.float32, device=self.device)
-        ws = ops.workspace(lib().tribe_w2vbert_workspace_bytes(C.byref(d)), self.device, "extractor")
-        check(lib().tribe_w2vbert_fwd(C.byref(d), states.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-              "tribe_w2vbert_fwd")
-        return states.permute(1, 0, 3, 2).contiguous()  # [B, n_states, dim, n_out]
+        return self._launch(d, states, fp8, _amax, "hidden_states_resampled").permute(1, 0, 3, 2).contiguous()  # [B, n_states, dim, n_out]
 
 
 class HipFbank:

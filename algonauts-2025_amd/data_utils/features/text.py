@@ -27,8 +27,9 @@ import pydantic
 import torch
 
 from tribe_hip import _lib, ops
-from tribe_hip._lib import LlamaDesc, LlamaLayer, check, lib
+from tribe_hip._lib import LlamaDesc, LlamaFp8Layer, LlamaLayer
 
+from .extractor_host import ExtractorHost
 from .plugin import HbmFeaturePlugin
 
 # Llama-3.2-3B hyper-parameters (public model card; not verifiable offline -> configuration input)
@@ -61,11 +62,16 @@ def rope_inv_freq(head_dim: int, rope: dict[str, tp.Any]) -> torch.Tensor:
     return torch.where(medium, smoothed, scaled)
 
 
-class HipLlamaModel:
-    """Packed bf16 weights of a LlamaModel + the forward-with-pooling launcher."""
+class HipLlamaModel(ExtractorHost):
+    """Packed bf16 weights of a LlamaModel + the forward-with-pooling launcher.  enable_fp8(calibration_ids [B, T]) switches the four
+    Linear GEMMs of every layer to e4m3; its amax table columns are qkv in, o_proj in, gate_up in, down in."""
+
+    FORWARD, FP8_LAYER, FP8_FIELDS = "tribe_llama_fwd", LlamaFp8Layer, ("w_qkv", "w_o", "w_gate_up", "w_down")
+    FP8_WIDTHS_ERROR = "fp8 path: hidden_size, num_attention_heads * head_dim and intermediate_size must be multiples of 128"
 
     def __init__(self, config: tp.Any, state_dict: dict[str, torch.Tensor], device: str | torch.device = "cuda"):
-        g = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
+        super().__init__(config, {k.removeprefix("model."): v for k, v in state_dict.items()}, device)
+        g, f32, own = self.cfg, self.f32, self.own
         self.dim, self.depth, self.inter = g("hidden_size"), g("num_hidden_layers"), g("intermediate_size")
         self.heads_q, self.heads_kv = g("num_attention_heads"), g("num_key_value_heads")
         try:
@@ -78,23 +84,10 @@ class HipLlamaModel:
         except (KeyError, AttributeError):
             rope = None
         self.inv_freq = rope_inv_freq(self.dim_head, dict(rope) if rope else {"rope_type": "default", "rope_theta": 10000.0})
-        self.device = torch.device(device)
-        sd = {k.removeprefix("model."): v for k, v in state_dict.items()}
-        dev = self.device
-
-        def f32(name: str) -> torch.Tensor:
-            return sd[name].detach().to(device=dev, dtype=torch.float32).contiguous()
-
-        self.keep: list[torch.Tensor] = []
-
-        def own(t: torch.Tensor) -> int:
-            self.keep.append(t)
-            return t.data_ptr()
-
+        self.fp8_widths = (self.dim, self.heads_q * self.dim_head, self.inter)
         self.embed = f32("embed_tokens.weight").to(torch.bfloat16).contiguous()  # bf16 table: 0.79 GB for the 3B vocab
         self.layers = (LlamaLayer * max(self.depth, 1))()
         self.packs: list[tuple[torch.Tensor, ...]] = []      # bf16 (qkv, o, gate_up, down) per layer, the source of the fp8 packs
-        self.fp8_layers = None                               # LlamaFp8Layer array once enable_fp8() has run
         for i in range(self.depth):
             p = f"layers.{i}."
             L = self.layers[i]
@@ -109,6 +102,7 @@ class HipLlamaModel:
             L.post_norm_w = own(f32(p + "post_attention_layernorm.weight"))
             del wqkv, gate, up, gate_up
         self.final_norm = f32("norm.weight")
+        del self._sd
         self._tabs: dict[int, tuple[torch.Tensor, torch.Tensor]] = {}
 
     def _tables(self, T: int) -> tuple[torch.Tensor, torch.Tensor]:
@@ -117,33 +111,10 @@ class HipLlamaModel:
             self._tabs[T] = (freqs.cos().to(self.device).contiguous(), freqs.sin().to(self.device).contiguous())
         return self._tabs[T]
 
-    def enable_fp8(self, calibration_ids: torch.Tensor, margin: float = 1.0) -> torch.Tensor:
-        """Switch the four Linear GEMMs of every layer to e4m3 (BASELINE config 5): per-tensor weight scales amax / 448 and
-        static per-tensor input scales from one bf16 calibration pass over `calibration_ids` [B, T] (amax * margin / 448).
-        Returns the calibration amax table f32 [depth, 4] (qkv in, o_proj in, gate_up in, down in)."""
-        if any(v % 128 for v in (self.dim, self.heads_q * self.dim_head, self.inter)):
-            raise ValueError("fp8 path: hidden_size, num_attention_heads * head_dim and intermediate_size must be multiples of 128")
-        self.fp8_layers = None
-        amax = torch.zeros(max(self.depth, 1), 4, dtype=torch.float32, device=self.device)
+    def _calibrate(self, calibration_ids: torch.Tensor, amax: torch.Tensor) -> None:
         B, T = calibration_ids.shape
         zeros, full = torch.zeros(B, dtype=torch.int64), torch.full((B,), T, dtype=torch.int64)
         self.forward_pooled(calibration_ids, zeros, full, _amax=amax)
-        table = amax.cpu()                                    # one-time sync: the scales become launch constants
-        if not bool((table[: self.depth] > 0).all()):
-            raise ValueError("fp8 calibration saw an all-zero GEMM input")
-        layers = (_lib.LlamaFp8Layer * max(self.depth, 1))()
-        self.fp8_packs = []
-        for i in range(self.depth):
-            q = []
-            for j, w in enumerate(self.packs[i]):
-                w_scale = float(ops.absmax(w)) / ops.FP8_MAX
-                q.append(ops.quantize_fp8(w, w_scale, K_pad=w.shape[1]))
-                layers[i].w_scale[j] = w_scale
-                layers[i].in_scale[j] = float(table[i, j]) * margin / ops.FP8_MAX
-            layers[i].w_qkv, layers[i].w_o, layers[i].w_gate_up, layers[i].w_down = (t.data_ptr() for t in q)
-            self.fp8_packs.append(q)
-        self.fp8_layers = layers
-        return table
 
     def forward_pooled(self, input_ids: torch.Tensor, pool_start: torch.Tensor, pool_len: torch.Tensor, fp8: bool | None = None,
                        _amax: torch.Tensor | None = None) -> torch.Tensor:
@@ -165,18 +136,8 @@ class HipLlamaModel:
         d.final_norm_w = self.final_norm.data_ptr()
         d.cos_tab, d.sin_tab = cos.data_ptr(), sin.data_ptr()
         d.ids, d.pool_start, d.pool_len = ids.data_ptr(), start.data_ptr(), length.data_ptr()
-        use_fp8 = (self.fp8_layers is not None) if fp8 is None else fp8
-        if use_fp8 and _amax is None:
-            if self.fp8_layers is None:
-                raise ValueError("forward_pooled(fp8=True) before enable_fp8()")
-            d.fp8_host = C.cast(self.fp8_layers, C.POINTER(_lib.LlamaFp8Layer))
-        if _amax is not None:
-            d.amax_out = _amax.data_ptr()
         states = torch.empty(self.depth + 1, B, self.dim, dtype=torch.float32, device=self.device)
-        ws = ops.workspace(lib().tribe_llama_workspace_bytes(C.byref(d)), self.device, "extractor")
-        check(lib().tribe_llama_fwd(C.byref(d), states.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-              "tribe_llama_fwd")
-        return states
+        return self._launch(d, states, fp8, _amax, "forward_pooled")
 
 
 def word_pool_windows(input_ids: torch.Tensor, target_words: tp.Sequence[str], pad_id: int) -> tuple[torch.Tensor, torch.Tensor]:

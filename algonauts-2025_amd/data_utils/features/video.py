@@ -19,8 +19,9 @@ import pydantic
 import torch
 
 from tribe_hip import ops
-from tribe_hip._lib import Vjepa2Desc, VitLayer, check, lib
+from tribe_hip._lib import VitFp8Layer, VitLayer, Vjepa2Desc
 
+from .extractor_host import ExtractorHost
 from .plugin import HbmFeaturePlugin
 
 # facebook/vjepa2-vitg-fpc64-256 hyper-parameters (public model card; configuration input, not verifiable offline)
@@ -49,34 +50,28 @@ def rope3d_tables(grid_depth: int, grid_size: int, dim_head: int) -> tuple[torch
     return cos.contiguous(), sin.contiguous()
 
 
-class HipVJEPA2Encoder:
+class HipVJEPA2Encoder(ExtractorHost):
+    """Packed bf16 weights of the V-JEPA2 encoder + the forward-with-token-mean launcher.  enable_fp8(calibration_clip
+    [B, frames, C, H, W]) switches the four Linear GEMMs of every layer to e4m3 (amax table columns: qkv, proj, fc1, fc2 in)."""
+
+    FORWARD, FP8_LAYER, FP8_FIELDS = "tribe_vjepa2_fwd", VitFp8Layer, ("w_qkv", "w_proj", "w_fc1", "w_fc2")
+    FP8_WIDTHS_ERROR = "fp8 path: hidden_size and the MLP width must be multiples of 128"
+    MISSING_WEIGHTS_ARE_NONE = True    # qkv_bias=False checkpoints
+
     def __init__(self, config: tp.Any, state_dict: dict[str, torch.Tensor], device: str | torch.device = "cuda"):
-        g = (lambda k: config[k]) if isinstance(config, dict) else (lambda k: getattr(config, k))
+        super().__init__(config, {k.removeprefix("encoder."): v for k, v in state_dict.items() if not k.startswith("predictor.")}, device)
+        g, f32, own = self.cfg, self.f32, self.own
         self.patch, self.crop, self.frames, self.tubelet = g("patch_size"), g("crop_size"), g("frames_per_clip"), g("tubelet_size")
         self.dim, self.chans, self.heads, self.depth = g("hidden_size"), g("in_chans"), g("num_attention_heads"), g("num_hidden_layers")
         self.mlp = int(self.dim * g("mlp_ratio"))
         self.eps = float(g("layer_norm_eps"))
         self.dim_head = self.dim // self.heads
-        self.device = dev = torch.device(device)
-        sd = {k.removeprefix("encoder."): v for k, v in state_dict.items() if not k.startswith("predictor.")}
-
-        def f32(name: str) -> torch.Tensor | None:
-            return sd[name].detach().to(device=dev, dtype=torch.float32).contiguous() if name in sd else None
-
-        self.keep: list[torch.Tensor] = []
-
-        def own(t: torch.Tensor | None) -> int | None:
-            if t is None:
-                return None
-            self.keep.append(t)
-            return t.data_ptr()
-
+        self.fp8_widths = (self.dim, self.mlp)
         wp = f32("embeddings.patch_embeddings.proj.weight")  # [dim, C, tub, p, p]
         self.w_patch = ops.pack_weight(wp.reshape(self.dim, -1).contiguous())
         self.b_patch = f32("embeddings.patch_embeddings.proj.bias")
         self.layers = (VitLayer * max(self.depth, 1))()
         self.packs: list[tuple[torch.Tensor, ...]] = []      # bf16 (qkv, proj, fc1, fc2) per layer, the source of the fp8 packs
-        self.fp8_layers = None                               # VitFp8Layer array once enable_fp8() has run
         for i in range(self.depth):
             p = f"layer.{i}."
             L = self.layers[i]
@@ -92,33 +87,10 @@ class HipVJEPA2Encoder:
             L.norm2_w, L.norm2_b = own(f32(p + "norm2.weight")), own(f32(p + "norm2.bias"))
             L.b_fc1, L.b_fc2 = own(f32(p + "mlp.fc1.bias")), own(f32(p + "mlp.fc2.bias"))
         self._tabs: dict[tuple[int, int], tuple[torch.Tensor, torch.Tensor]] = {}
+        del self._sd
 
-    def enable_fp8(self, calibration_clip: torch.Tensor, margin: float = 1.0) -> torch.Tensor:
-        """e4m3 Linear GEMMs (BASELINE config 5), as HipLlamaModel.enable_fp8: per-tensor weight scales, static input scales
-        from one bf16 pass over `calibration_clip` [B, frames, C, H, W].  Returns the amax table f32 [depth, 4]."""
-        from tribe_hip._lib import VitFp8Layer
-
-        if self.dim % 128 or self.mlp % 128:
-            raise ValueError("fp8 path: hidden_size and the MLP width must be multiples of 128")
-        self.fp8_layers = None
-        amax = torch.zeros(max(self.depth, 1), 4, dtype=torch.float32, device=self.device)
+    def _calibrate(self, calibration_clip: torch.Tensor, amax: torch.Tensor) -> None:
         self.hidden_state_means(calibration_clip, _amax=amax)
-        table = amax.cpu()
-        if not bool((table[: self.depth] > 0).all()):
-            raise ValueError("fp8 calibration saw an all-zero GEMM input")
-        layers = (VitFp8Layer * max(self.depth, 1))()
-        self.fp8_packs = []
-        for i in range(self.depth):
-            q = []
-            for j, w in enumerate(self.packs[i]):
-                w_scale = float(ops.absmax(w)) / ops.FP8_MAX
-                q.append(ops.quantize_fp8(w, w_scale, K_pad=w.shape[1]))
-                layers[i].w_scale[j] = w_scale
-                layers[i].in_scale[j] = float(table[i, j]) * margin / ops.FP8_MAX
-            layers[i].w_qkv, layers[i].w_proj, layers[i].w_fc1, layers[i].w_fc2 = (t.data_ptr() for t in q)
-            self.fp8_packs.append(q)
-        self.fp8_layers = layers
-        return table
 
     def hidden_state_means(self, pixel_values_videos: torch.Tensor, fp8: bool | None = None, _amax: torch.Tensor | None = None) -> torch.Tensor:
         """pixel_values_videos f32 [B, frames, C, H, W] -> f32 [B, depth + 1, dim] (video.py:262-268 + :228).
@@ -140,18 +112,8 @@ class HipVJEPA2Encoder:
         d.w_patch, d.b_patch, d.K_pad = self.w_patch.data_ptr(), ops._p(self.b_patch), self.w_patch.shape[1]
         d.layers_host = C.cast(self.layers, C.POINTER(VitLayer))
         d.cos_tab, d.sin_tab, d.pixels = cos.data_ptr(), sin.data_ptr(), pix.data_ptr()
-        use_fp8 = (self.fp8_layers is not None) if fp8 is None else fp8
-        if use_fp8 and _amax is None:
-            if self.fp8_layers is None:
-                raise ValueError("hidden_state_means(fp8=True) before enable_fp8()")
-            d.fp8_host = C.cast(self.fp8_layers, C.POINTER(type(self.fp8_layers[0])))
-        if _amax is not None:
-            d.amax_out = _amax.data_ptr()
         states = torch.empty(self.depth + 1, B, self.dim, dtype=torch.float32, device=self.device)
-        ws = ops.workspace(lib().tribe_vjepa2_workspace_bytes(C.byref(d)), self.device, "extractor")
-        check(lib().tribe_vjepa2_fwd(C.byref(d), states.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream),
-              "tribe_vjepa2_fwd")
-        return states.transpose(0, 1).contiguous()
+        return self._launch(d, states, fp8, _amax, "hidden_state_means").transpose(0, 1).contiguous()
 
 
 def default_video_processor(frames: np.ndarray, crop_size: int = 256) -> torch.Tensor:

@@ -13,13 +13,12 @@ model.py:113-174 (forward graph), x_transformers encoder (oracle/xt_encoder.py).
 
 from __future__ import annotations
 
-import ctypes as C
 import typing as tp
 
 import torch
 
 from tribe_hip import _lib, ops
-from tribe_hip._lib import BF16, F32, GemmDesc, check, lib
+from tribe_hip._lib import BF16, F32, ROLE, check, lib
 
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 
@@ -27,43 +26,8 @@ _DT = {torch.float32: F32, torch.bfloat16: BF16}
 _LOG2E = 1.4426950408889634
 
 
-def _s() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, *, lda=None, ldb=None, ldc=None, M=None, N=None, K=None, alpha=1.0,
-          bias=None, act=_lib.ACT_NONE, aux=None, res=None, ldres=None, res_scale=None, batch1=1, batch0=1, sA=(0, 0), sB=(0, 0), sC=(0, 0),
-          gather1=None, gather_a=False, gather_b=False, a_off=0, b_off=0, c_off=0, role=0, trans_ab=False, row_bias=None, row_bias_off=0,
-          sBias=(0, 0), ld_aux=None, stream_k=False) -> None:
-    """Thin positional wrapper over tribe_gemm_bf16 (element offsets allow strided views without copies).
-    stream_k (trans_ab only): let the launcher cut the last partial round of tiles over all CUs (workspace taken from ops.workspace)."""
-    d = GemmDesc()
-    d.trans_ab = int(trans_ab)
-    d.stream_k = int(stream_k)
-    d.M, d.N, d.K, d.batch1, d.batch0 = M, N, K, batch1, batch0
-    d.A, d.lda, d.sA1, d.sA0 = a.data_ptr() + 2 * a_off, lda, sA[0], sA[1]
-    d.B, d.ldb, d.sB1, d.sB0 = b.data_ptr() + 2 * b_off, ldb, sB[0], sB[1]
-    d.C, d.ldc, d.sC1, d.sC0 = out.data_ptr() + out.element_size() * c_off, ldc, sC[0], sC[1]
-    d.c_dtype, d.alpha, d.act, d.role = _DT[out.dtype], alpha, act, role
-    if bias is not None:
-        d.bias, d.bias_mode = bias.data_ptr(), _lib.BIAS_COL
-    if row_bias is not None:   # f32 per output row, batch strides sBias (elements)
-        d.bias, d.bias_mode, d.sBias1, d.sBias0 = row_bias.data_ptr() + 4 * row_bias_off, _lib.BIAS_ROW, sBias[0], sBias[1]
-    if aux is not None:
-        d.aux, d.ld_aux = aux.data_ptr(), (ld_aux if ld_aux is not None else N)
-    if res is not None:
-        d.res, d.ldres = res.data_ptr() + 4 * c_off, (ldres if ldres is not None else ldc)
-        d.sRes1, d.sRes0 = sC
-    if res_scale is not None:
-        d.res_scale = res_scale.data_ptr()
-    if gather1 is not None:
-        d.gather1, d.gather_a, d.gather_b = gather1.data_ptr(), int(gather_a), int(gather_b)
-    if stream_k:
-        nbytes = lib().tribe_gemm_stream_k_workspace_bytes(C.byref(d))
-        if nbytes > 0:   # parts of split tiles travel through the workspace; a second launch sums them in order
-            ws = ops.workspace(nbytes, out.device, tag="streamk")
-            d.stream_k_ws, d.stream_k_ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    check(lib().tribe_gemm_bf16(C.byref(d), _s()), "tribe_gemm_bf16")
+_s = ops._stream
+_gemm = ops._gemm   # the one GEMM launcher (tribe_hip/ops.py)
 
 
 def transpose_bf16(x: torch.Tensor, Z: int, R: int, Cc: int, s_z: int, s_r: int, off: int = 0) -> torch.Tensor:
@@ -106,6 +70,35 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, M: int, N: int, K
     x_t = transpose_bf16(x, 1, M, K, 0, ld_x)[0]      # [K, M_pad]
     Mp = dy_t.shape[1]
     _gemm(dy_t, x_t, dw, lda=Mp, ldb=Mp, ldc=K, M=N, N=K, K=Mp)
+
+
+def dense_bwd(dpre: torch.Tensor, x: torch.Tensor, wt: torch.Tensor, N: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """(dx, dw) of y = x W^T from dpre = dy as bf16 [M, N]: x bf16 [M, K], wt = W^T bf16 [K, N_pad64] (the second half of a pack).
+    dx is bf16 like x (autograd would cast an f32 gradient in a pass of its own), dw f32 [N, K]."""
+    M, K = x.shape
+    Np = wt.shape[1]
+    if Np != N:
+        dpre = torch.nn.functional.pad(dpre, (0, Np - N))  # zero K-padding for the dgrad GEMM (N % 64 != 0 only)
+    dx = torch.empty(M, K, dtype=x.dtype, device=x.device)
+    _gemm(dpre, wt, dx, lda=Np, ldb=Np, ldc=K, M=M, N=K, K=Np)
+    dw = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    wgrad(dpre, x, dw, M, N, K, Np, K)   # dW[n, k] = sum_m dpre[m, n] x[m, k]
+    return dx, dw
+
+
+def res_grad(dy: torch.Tensor, res: torch.Tensor, res_scale: torch.Tensor | None, raw: bool) -> torch.Tensor:
+    """Gradient of the residual input of y = ... + res * res_scale from dy f32 [M, N]; raw: the residual came from ScaleNormFork,
+    which applies res_scale to its gradient itself, so dy goes back as it is."""
+    if raw:
+        return dy
+    dres = torch.empty_like(res)
+    check(lib().tribe_scale_cols_fwd(dy.data_ptr(), ops._p(res_scale), dy.shape[0], dy.shape[1], dres.data_ptr(), _s()), "tribe_scale_cols_fwd")
+    return dres
+
+
+def upstream_scale(g: torch.Tensor) -> torch.Tensor:
+    """The gradient arriving at a scalar loss as the f32 [1] device tensor its backward kernel reads."""
+    return g.reshape(1).to(torch.float32).contiguous()
 
 
 def colsum(a: torch.Tensor, M: int, N: int, b: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -170,7 +163,7 @@ class Linear(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, res, res_scale, out_f32: bool, raw_res_grad: bool = False):
-        ctx.raw_res_grad = raw_res_grad   # the residual came from ScaleNormFork, which applies res_scale to its gradient itself
+        ctx.raw_res_grad = raw_res_grad   # see res_grad
         M, K = x.shape
         N = w.shape[0]
         wp, _ = PACKS.get(w)
@@ -189,24 +182,10 @@ class Linear(torch.autograd.Function):
         M, K = x.shape
         N = w.shape[0]
         dy = dy.contiguous()
-        dres = drs = None
-        if res is not None:
-            if ctx.raw_res_grad:
-                dres = dy
-            else:
-                dres = torch.empty_like(res)
-                check(lib().tribe_scale_cols_fwd(dy.data_ptr(), ops._p(res_scale), M, N, dres.data_ptr(), _s()), "tribe_scale_cols_fwd")
+        dres = res_grad(dy, res, res_scale, ctx.raw_res_grad) if res is not None else None
         # bias gradient, res_scale gradient and the bf16 GEMM operand from ONE pass over dy
         db, drs, dpre = grad_sums_and_cast(dy, M, N, res=res if (res is not None and res_scale is not None) else None, want_sum=ctx.has_b)
-        _, wt = PACKS.get(w)  # [K, N_pad64]
-        Np = wt.shape[1]
-        if Np != N:
-            dpre = torch.nn.functional.pad(dpre, (0, Np - N))  # zero K-padding for the dgrad GEMM (N % 64 != 0 only)
-        dx = torch.empty(M, K, dtype=x.dtype, device=x.device)   # x is bf16: autograd would cast an f32 gradient in a pass of its own
-        _gemm(dpre, wt, dx, lda=Np, ldb=Np, ldc=K, M=M, N=K, K=Np)
-        # dW[n, k] = sum_m dpre[m, n] x[m, k]
-        dw = torch.empty(N, K, dtype=torch.float32, device=x.device)
-        wgrad(dpre, x, dw, M, N, K, Np, K)
+        dx, dw = dense_bwd(dpre, x, PACKS.get(w)[1], N)
         dw = dw[:, : w.shape[1]] if w.shape[1] != K else dw
         return dx, dw, db, dres, drs, None, None
 
@@ -276,24 +255,16 @@ class QKVLinear(torch.autograd.Function):
         N = wq.shape[0]
         wp, _ = QKV_PACKS.get((wq, wk, wv))
         y = torch.empty(M, 3 * N, dtype=torch.bfloat16, device=x.device)
-        _gemm(x, wp, y, lda=K, ldb=K, ldc=3 * N, M=M, N=3 * N, K=K, role=2)
+        _gemm(x, wp, y, lda=K, ldb=K, ldc=3 * N, M=M, N=3 * N, K=K, role=ROLE["qkv"])
         ctx.save_for_backward(x, wq, wk, wv)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, wq, wk, wv = ctx.saved_tensors
-        M, K = x.shape
         N = wq.shape[0]
         _, wt = QKV_PACKS.get((wq, wk, wv))                     # [K, 3N_pad64]
-        dpre = cast_bf16(dy.contiguous())
-        N3, Np = 3 * N, wt.shape[1]
-        if Np != N3:
-            dpre = torch.nn.functional.pad(dpre, (0, Np - N3))
-        dx = torch.empty(M, K, dtype=x.dtype, device=x.device)   # x is bf16: autograd would cast an f32 gradient in a pass of its own
-        _gemm(dpre, wt, dx, lda=Np, ldb=Np, ldc=K, M=M, N=K, K=Np)
-        dw = torch.empty(N3, K, dtype=torch.float32, device=x.device)
-        wgrad(dpre, x, dw, M, N3, K, Np, K)
+        dx, dw = dense_bwd(cast_bf16(dy.contiguous()), x, wt, 3 * N)
         return dx, dw[:N], dw[N:2 * N], dw[2 * N:]
 
 
@@ -310,9 +281,9 @@ class FeedForward(torch.autograd.Function):
         w2p, _ = PACKS.get(w2)
         pre = torch.empty(M, Fh, dtype=torch.bfloat16, device=x.device)
         h = torch.empty(M, Fh, dtype=torch.bfloat16, device=x.device)
-        _gemm(x, w1p, h, lda=D, ldb=D, ldc=Fh, M=M, N=Fh, K=D, bias=b1, act=_lib.ACT_GELU, aux=pre, role=6)
+        _gemm(x, w1p, h, lda=D, ldb=D, ldc=Fh, M=M, N=Fh, K=D, bias=b1, act=_lib.ACT_GELU, aux=pre, role=ROLE["ff1"])
         out = torch.empty(M, D, dtype=torch.float32, device=x.device)
-        _gemm(h, w2p, out, lda=Fh, ldb=Fh, ldc=D, M=M, N=D, K=Fh, bias=b2, res=res, res_scale=res_scale, role=7)
+        _gemm(h, w2p, out, lda=Fh, ldb=Fh, ldc=D, M=M, N=D, K=Fh, bias=b2, res=res, res_scale=res_scale, role=ROLE["ff2"])
         ctx.save_for_backward(x, w1, w2, pre, h, res, res_scale)
         return out
 
@@ -322,11 +293,7 @@ class FeedForward(torch.autograd.Function):
         M, D = x.shape
         Fh = w1.shape[0]
         dout = dout.contiguous()
-        if ctx.raw_res_grad:
-            dres = dout
-        else:
-            dres = torch.empty_like(res)
-            check(lib().tribe_scale_cols_fwd(dout.data_ptr(), ops._p(res_scale), M, D, dres.data_ptr(), _s()), "tribe_scale_cols_fwd")
+        dres = res_grad(dout, res, res_scale, ctx.raw_res_grad)
         db2, drs, dob = grad_sums_and_cast(dout, M, D, res=res if res_scale is not None else None, want_sum=True)   # one pass over dout
         _, w2t = PACKS.get(w2)                                  # [Fh, D]
         dpre = torch.empty(M, Fh, dtype=torch.bfloat16, device=x.device)
@@ -334,11 +301,7 @@ class FeedForward(torch.autograd.Function):
         dw2 = torch.empty(D, Fh, dtype=torch.float32, device=x.device)
         wgrad(dob, h, dw2, M, D, Fh, D, Fh)
         db1 = colsum(dpre, M, Fh)
-        _, w1t = PACKS.get(w1)                                  # [D, Fh]
-        dx = torch.empty(M, D, dtype=x.dtype, device=x.device)   # as in Linear.backward
-        _gemm(dpre, w1t, dx, lda=Fh, ldb=Fh, ldc=D, M=M, N=D, K=Fh)
-        dw1 = torch.empty(Fh, D, dtype=torch.float32, device=x.device)
-        wgrad(dpre, x, dw1, M, Fh, D, Fh, D)
+        dx, dw1 = dense_bwd(dpre, x, PACKS.get(w1)[1], Fh)      # (no pad: ff_inner % 64 == 0)
         return dx, dw1, db1, dw2, db2, dres, drs, None
 
 
@@ -625,7 +588,7 @@ class MSE(torch.autograd.Function):
     def backward(ctx, g):
         pred, true = ctx.saved_tensors
         dp = torch.empty_like(pred)
-        g = g.reshape(1).to(torch.float32).contiguous()
+        g = upstream_scale(g)
         check(lib().tribe_mse_bwd(pred.data_ptr(), true.data_ptr(), pred.numel(), g.data_ptr(), dp.data_ptr(), _s()), "tribe_mse_bwd")
         return dp, None
 
@@ -644,7 +607,7 @@ class ElemLoss(torch.autograd.Function):
     def backward(ctx, g):
         pred, true = ctx.saved_tensors
         dp = torch.empty_like(pred)
-        g = g.reshape(1).to(torch.float32).contiguous()
+        g = upstream_scale(g)
         check(lib().tribe_elem_loss_bwd(pred.data_ptr(), true.data_ptr(), pred.numel(), ops.ELEM_LOSS_KINDS[ctx.kind], ctx.param,
                                         ops.ELEM_LOSS_REDUCTIONS[ctx.reduction], g.data_ptr(), dp.data_ptr(), _s()), "tribe_elem_loss_bwd")
         return dp, None, None, None, None
@@ -668,7 +631,7 @@ class PearsonLossFn(torch.autograd.Function):
         stats = torch.zeros(1, V, 6, dtype=torch.float64, device=pred.device)
         ops.pearson_stats_update(stats, pred, true)
         dp = torch.empty(B, V, T, dtype=torch.float32, device=pred.device)
-        g = g.reshape(1).to(torch.float32).contiguous()
+        g = upstream_scale(g)
         check(lib().tribe_pearson_loss_bwd(pred.data_ptr(), true.data_ptr(), B, V, T, sb, sv, st, stats.data_ptr(), int(ctx.reduction == "sum"),
                                            g.data_ptr(), dp.data_ptr(), _s()), "tribe_pearson_loss_bwd")
         if (sb, sv, st) != (V * T, T, 1):  # gradient in the layout of the (strided) input view
@@ -737,7 +700,7 @@ class ProjectorFuse(torch.autograd.Function):
         N = w.shape[0]
         wp, _ = PACKS.get(w)
         y = torch.empty(M, N, dtype=torch.float32, device=feat.device)
-        _gemm(feat, wp, y, lda=Kp, ldb=Kp, ldc=N, M=M, N=N, K=Kp, bias=b, role=1)
+        _gemm(feat, wp, y, lda=Kp, ldb=Kp, ldc=N, M=M, N=N, K=Kp, bias=b, role=ROLE["projector"])
         ctx.save_for_backward(feat, w)
         return y
 

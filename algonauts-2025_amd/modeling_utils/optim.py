@@ -14,7 +14,7 @@ import typing as tp
 import numpy as np
 import torch
 
-from tribe_hip import _lib
+from tribe_hip import _lib, ops
 from tribe_hip._lib import check, lib
 
 from . import shadow
@@ -90,7 +90,7 @@ class HipAdam(torch.optim.Optimizer):
                 keep_alive.append(table_t)
                 check(lib().tribe_adam_step(table_t.data_ptr(), owner.data_ptr(), start.data_ptr(), owner.numel(), float(group["lr"]), float(b1),
                                             float(b2), float(group["eps"]), float(group["weight_decay"]), step, int(group["decoupled_weight_decay"]),
-                                            torch.cuda.current_stream().cuda_stream), "tribe_adam_step")
+                                            ops._stream()), "tribe_adam_step")
                 # the kernel wrote through raw pointers: tell autograd (and this build's packed-weight caches, which key on
                 # `_version`) that the parameters changed
                 torch.autograd.graph.increment_version(params)

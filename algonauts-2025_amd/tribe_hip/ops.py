@@ -60,6 +60,53 @@ def workspace(nbytes: int, device: torch.device, tag: str = "main") -> torch.Ten
 # --------------------------------------------------------------------------------------
 # generic MFMA GEMM
 # --------------------------------------------------------------------------------------
+_ACT = {"gelu": _lib.ACT_GELU, "swiglu": _lib.ACT_SWIGLU, "silu": _lib.ACT_SILU, "glu": _lib.ACT_GLU, None: _lib.ACT_NONE}
+
+
+def _gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, *, lda=None, ldb=None, ldc=None, M=None, N=None, K=None, alpha=1.0,
+          bias=None, act=_lib.ACT_NONE, aux=None, res=None, ldres=None, res_scale=None, batch1=1, batch0=1, sA=(0, 0), sB=(0, 0), sC=(0, 0),
+          gather1=None, gather_a=False, gather_b=False, a_off=0, b_off=0, c_off=0, role=_lib.ROLE["generic"], trans_ab=False,
+          row_bias=None, row_bias_off=0, sBias=(0, 0), ld_aux=None, stream_k=False, sRes=None, rowadd=None, rowadd_period=0,
+          gadd=None, gadd_index=None, gadd_div=0, tile_hint=0, fp8=False) -> bool:
+    """The one place a tribe_gemm_desc is filled and launched (tribe_gemm_bf16; fp8: tribe_gemm_fp8 on e4m3 bytes).  Element offsets and
+    batch strides allow strided views without copies.  N is the width of the product: a gated activation (SwiGLU / GLU) stores N / 2
+    columns, so its caller passes ldc (and sC) for the stored width while the residual keeps ldres / sRes (default: ldc / sC).
+    bias: f32 per output column; row_bias: f32 per output row, batch strides sBias (elements).
+    stream_k: let the launcher share the reduction of tiles out over workgroups (workspace taken from `workspace`); returns whether it did."""
+    d = GemmDesc(M=M, N=N, K=K, batch1=batch1, batch0=batch0,
+                 A=a.data_ptr() + a.element_size() * a_off, lda=lda, sA1=sA[0], sA0=sA[1],
+                 B=b.data_ptr() + b.element_size() * b_off, ldb=ldb, sB1=sB[0], sB0=sB[1],
+                 C=out.data_ptr() + out.element_size() * c_off, ldc=ldc, sC1=sC[0], sC0=sC[1],
+                 c_dtype=_DT[out.dtype], alpha=alpha, act=act, role=role, tile_hint=tile_hint, trans_ab=int(trans_ab), stream_k=int(stream_k))
+    if bias is not None:
+        d.bias, d.bias_mode = bias.data_ptr(), _lib.BIAS_COL
+    if row_bias is not None:
+        d.bias, d.bias_mode, d.sBias1, d.sBias0 = row_bias.data_ptr() + 4 * row_bias_off, _lib.BIAS_ROW, sBias[0], sBias[1]
+    if aux is not None:
+        d.aux, d.ld_aux = aux.data_ptr(), (ld_aux if ld_aux is not None else N)
+    if res is not None:
+        d.res, d.ldres = res.data_ptr() + 4 * c_off, (ldres if ldres is not None else ldc)
+        d.sRes1, d.sRes0 = sC if sRes is None else sRes
+    if res_scale is not None:
+        d.res_scale = res_scale.data_ptr()
+    if gather1 is not None:
+        d.gather1, d.gather_a, d.gather_b = gather1.data_ptr(), int(gather_a), int(gather_b)
+    if rowadd is not None:
+        d.rowadd, d.ld_rowadd, d.rowadd_period = rowadd.data_ptr(), rowadd.shape[-1], rowadd_period
+    if gadd is not None:
+        d.gadd, d.gadd_index, d.gadd_div, d.ld_gadd = gadd.data_ptr(), gadd_index.data_ptr(), gadd_div, gadd.shape[-1]
+    split = False
+    if stream_k:
+        nbytes = lib().tribe_gemm_stream_k_workspace_bytes(C.byref(d))
+        split = nbytes > 0
+        if split:   # parts of split tiles travel through the workspace; a second launch sums them in order
+            ws = workspace(nbytes, out.device, tag="streamk")
+            d.stream_k_ws, d.stream_k_ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    what = "tribe_gemm_fp8" if fp8 else "tribe_gemm_bf16"
+    check(getattr(lib(), what)(C.byref(d), _stream()), what)
+    return split
+
+
 def gemm_nt(
     a: torch.Tensor, b: torch.Tensor, *, bias: torch.Tensor | None = None, bias_row: bool = False, act: str | None = None,
     res: torch.Tensor | None = None, res_scale: torch.Tensor | None = None, alpha: float = 1.0,
@@ -85,39 +132,16 @@ def gemm_nt(
     if out is None:
         out = torch.empty((Z, M, n_out) if a.ndim == 3 else (M, n_out), dtype=out_dtype, device=a.device)
     _cuda(out, (torch.float32, torch.bfloat16), "out")
-    d = GemmDesc()
-    d.M, d.N, d.K, d.batch1, d.batch0 = M, N, K, Z, 1
-    d.A, d.lda, d.sA1 = a3.data_ptr(), K, M * K
-    d.B, d.ldb, d.sB1 = b3.data_ptr(), K, N * K
-    d.C, d.ldc, d.sC1 = out.data_ptr(), n_out, M * n_out
-    d.c_dtype = _DT[out.dtype]
-    d.alpha = alpha
-    d.tile_hint = tile_hint
-    if bias is not None:
-        _cuda(bias, torch.float32, "bias")
-        d.bias, d.bias_mode = bias.data_ptr(), (_lib.BIAS_ROW if bias_row else _lib.BIAS_COL)
-    d.act = {"gelu": _lib.ACT_GELU, "swiglu": _lib.ACT_SWIGLU, "silu": _lib.ACT_SILU, "glu": _lib.ACT_GLU, None: _lib.ACT_NONE}[act]
-    if res is not None:
-        _cuda(res, torch.float32, "res")
-        d.res, d.ldres, d.sRes1 = res.data_ptr(), N, M * N
-    if res_scale is not None:
-        d.res_scale = _cuda(res_scale, torch.float32, "res_scale").data_ptr()
-    if rowadd is not None:
-        _cuda(rowadd, torch.float32, "rowadd")
-        d.rowadd, d.ld_rowadd, d.rowadd_period = rowadd.data_ptr(), rowadd.shape[-1], rowadd_period
-    if gadd is not None:
-        _cuda(gadd, torch.float32, "gadd")
-        _cuda(gadd_index, torch.int64, "gadd_index")
-        d.gadd, d.gadd_index, d.gadd_div, d.ld_gadd = gadd.data_ptr(), gadd_index.data_ptr(), gadd_div, gadd.shape[-1]
-    gemm_nt.last_split = False
-    if split_k:
-        d.stream_k = 1
-        nbytes = lib().tribe_gemm_stream_k_workspace_bytes(C.byref(d))
-        gemm_nt.last_split = nbytes > 0
-        if nbytes > 0:
-            ws = workspace(nbytes, a.device, tag="streamk")
-            d.stream_k_ws, d.stream_k_ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    check(lib().tribe_gemm_bf16(C.byref(d), _stream()), "tribe_gemm_bf16")
+    for name, t, dtype in (("bias", bias, torch.float32), ("res", res, torch.float32), ("res_scale", res_scale, torch.float32),
+                           ("rowadd", rowadd, torch.float32), ("gadd", gadd, torch.float32),
+                           ("gadd_index", gadd_index if gadd is not None else None, torch.int64)):
+        if t is not None:
+            _cuda(t, dtype, name)
+    gemm_nt.last_split = _gemm(
+        a3, b3, out, M=M, N=N, K=K, batch1=Z, lda=K, ldb=K, ldc=n_out, sA=(M * K, 0), sB=(N * K, 0), sC=(M * n_out, 0), alpha=alpha,
+        bias=None if bias_row else bias, row_bias=bias if bias_row else None, act=_ACT[act], res=res, ldres=N, sRes=(M * N, 0),
+        res_scale=res_scale, rowadd=rowadd, rowadd_period=rowadd_period, gadd=gadd, gadd_index=gadd_index, gadd_div=gadd_div,
+        tile_hint=tile_hint, stream_k=split_k)
     return out
 
 
@@ -136,19 +160,9 @@ def gemm_tn(at: torch.Tensor, bt: torch.Tensor, *, out_dtype: torch.dtype = torc
     K, M = at.shape
     N = bt.shape[1]
     out = torch.empty(M, N, dtype=out_dtype, device=at.device)
-    d = GemmDesc()
-    d.M, d.N, d.K, d.batch1, d.batch0 = M, N, K, 1, 1
-    d.A, d.lda, d.B, d.ldb = at.data_ptr(), M, bt.data_ptr(), N
-    d.C, d.ldc, d.c_dtype, d.alpha, d.trans_ab = out.data_ptr(), N, _DT[out_dtype], alpha, 1
     if bias is not None:
-        d.bias, d.bias_mode = _cuda(bias, torch.float32, "bias").data_ptr(), _lib.BIAS_COL
-    d.stream_k = int(stream_k)
-    nbytes = lib().tribe_gemm_stream_k_workspace_bytes(C.byref(d)) if stream_k else 0
-    gemm_tn.last_split = nbytes > 0
-    if nbytes > 0:   # parts of split tiles travel through the workspace; a second launch sums them in order
-        ws = workspace(nbytes, at.device, tag="streamk")
-        d.stream_k_ws, d.stream_k_ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    check(lib().tribe_gemm_bf16(C.byref(d), _stream()), "tribe_gemm_bf16")
+        _cuda(bias, torch.float32, "bias")
+    gemm_tn.last_split = _gemm(at, bt, out, M=M, N=N, K=K, lda=M, ldb=N, ldc=N, alpha=alpha, bias=bias, trans_ab=True, stream_k=stream_k)
     return out
 
 
@@ -267,6 +281,22 @@ def rotary_(qkv: torch.Tensor, T: int, heads: int, dim_head: int, rot_dim: int, 
     return qkv
 
 
+def _qkv_attention(qkv: torch.Tensor, B: int, T: int, heads_q: int, heads_kv: int, dim_head: int, scale: float, *, causal: bool = False,
+                   lse: torch.Tensor | None = None, rel_qe: torch.Tensor | None = None, rel_left: int = 0, rel_right: int = 0) -> torch.Tensor:
+    """tribe_attention_fwd_ex on a fused bf16 [B*T, (heads_q + 2*heads_kv) * dim_head] q|k|v buffer -> bf16 [B*T, heads_q * dim_head]:
+    the one place a tribe_attention_desc is filled.  lse: f32 [B, heads, T] to receive the base-2 log-sum-exp; rel_qe: f32
+    [B*T, heads, stride] relative-key bias table, clamped to offsets -rel_left .. rel_right."""
+    out = torch.empty(B * T, heads_q * dim_head, dtype=torch.bfloat16, device=qkv.device)
+    base, width = qkv.data_ptr(), (heads_q + 2 * heads_kv) * dim_head
+    d = AttentionDesc(q=base, k=base + 2 * heads_q * dim_head, v=base + 2 * (heads_q + heads_kv) * dim_head, ld_q=width, ld_k=width, ld_v=width,
+                      out=out.data_ptr(), ld_out=heads_q * dim_head, B=B, T=T, heads_q=heads_q, heads_kv=heads_kv, dim_head=dim_head,
+                      causal=int(causal), scale=scale, lse=_p(lse))
+    if rel_qe is not None:
+        d.rel_qe, d.ld_rel_qe, d.rel_stride_h, d.rel_left, d.rel_right = rel_qe.data_ptr(), heads_q * rel_qe.shape[2], rel_qe.shape[2], rel_left, rel_right
+    check(lib().tribe_attention_fwd_ex(C.byref(d), _stream()), "tribe_attention_fwd_ex")
+    return out
+
+
 def attention_gqa(qkv: torch.Tensor, B: int, T: int, heads_q: int, heads_kv: int, dim_head: int, scale: float,
                   causal: bool) -> torch.Tensor:
     """Fused attention on a [B*T, (heads_q + 2*heads_kv) * dim_head] q|k|v buffer (grouped-query, optional causal mask)."""
@@ -274,15 +304,7 @@ def attention_gqa(qkv: torch.Tensor, B: int, T: int, heads_q: int, heads_kv: int
     width = (heads_q + 2 * heads_kv) * dim_head
     if qkv.numel() != B * T * width:
         raise ValueError("attention_gqa: qkv has the wrong number of elements")
-    out = torch.empty(B * T, heads_q * dim_head, dtype=torch.bfloat16, device=qkv.device)
-    d = AttentionDesc()
-    base = qkv.data_ptr()
-    d.q, d.k, d.v = base, base + 2 * heads_q * dim_head, base + 2 * (heads_q + heads_kv) * dim_head
-    d.ld_q = d.ld_k = d.ld_v = width
-    d.out, d.ld_out = out.data_ptr(), heads_q * dim_head
-    d.B, d.T, d.heads_q, d.heads_kv, d.dim_head, d.causal, d.scale = B, T, heads_q, heads_kv, dim_head, int(causal), scale
-    check(lib().tribe_attention_fwd_ex(C.byref(d), _stream()), "tribe_attention_fwd_ex")
-    return out
+    return _qkv_attention(qkv, B, T, heads_q, heads_kv, dim_head, scale, causal=causal)
 
 
 def attention_relative_key(qkv: torch.Tensor, B: int, T: int, heads: int, dim_head: int, scale: float, qe: torch.Tensor,
@@ -294,16 +316,7 @@ def attention_relative_key(qkv: torch.Tensor, B: int, T: int, heads: int, dim_he
     _cuda(qe, torch.float32, "qe")
     if qkv.numel() != B * T * 3 * heads * dim_head or qe.dim() != 3 or qe.shape[0] != B * T or qe.shape[1] != heads:
         raise ValueError("attention_relative_key: qkv / qe have the wrong shape")
-    out = torch.empty(B * T, heads * dim_head, dtype=torch.bfloat16, device=qkv.device)
-    d = AttentionDesc()
-    base, width = qkv.data_ptr(), 3 * heads * dim_head
-    d.q, d.k, d.v = base, base + 2 * heads * dim_head, base + 4 * heads * dim_head
-    d.ld_q = d.ld_k = d.ld_v = width
-    d.out, d.ld_out = out.data_ptr(), heads * dim_head
-    d.B, d.T, d.heads_q, d.heads_kv, d.dim_head, d.causal, d.scale = B, T, heads, heads, dim_head, 0, scale
-    d.rel_qe, d.ld_rel_qe, d.rel_stride_h, d.rel_left, d.rel_right = qe.data_ptr(), heads * qe.shape[2], qe.shape[2], left, right
-    check(lib().tribe_attention_fwd_ex(C.byref(d), _stream()), "tribe_attention_fwd_ex")
-    return out
+    return _qkv_attention(qkv, B, T, heads, heads, dim_head, scale, rel_qe=qe, rel_left=left, rel_right=right)
 
 
 def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
@@ -391,17 +404,8 @@ def attention_with_lse(qkv: torch.Tensor, B: int, T: int, heads: int, dim_head: 
     inner = heads * dim_head
     if qkv.numel() != B * T * 3 * inner:
         raise ValueError("attention_with_lse: qkv has the wrong number of elements")
-    out = torch.empty(B * T, inner, dtype=torch.bfloat16, device=qkv.device)
     lse = torch.empty(B, heads, T, dtype=torch.float32, device=qkv.device)
-    d = AttentionDesc()
-    base = qkv.data_ptr()
-    d.q, d.k, d.v = base, base + 2 * inner, base + 4 * inner
-    d.ld_q = d.ld_k = d.ld_v = 3 * inner
-    d.out, d.ld_out = out.data_ptr(), inner
-    d.B, d.T, d.heads_q, d.heads_kv, d.dim_head, d.causal, d.scale = B, T, heads, heads, dim_head, 0, scale
-    d.lse = lse.data_ptr()
-    check(lib().tribe_attention_fwd_ex(C.byref(d), _stream()), "tribe_attention_fwd_ex")
-    return out, lse
+    return _qkv_attention(qkv, B, T, heads, heads, dim_head, scale, lse=lse), lse
 
 
 def rowdot_heads(a: torch.Tensor, b: torch.Tensor, B: int, T: int, heads: int, dim_head: int, scale: float) -> torch.Tensor:
@@ -866,16 +870,10 @@ def gemm_fp8_nt(a: torch.Tensor, b: torch.Tensor, alpha: float, *, bias: torch.T
     if out is None:
         out = torch.empty(M, n_out, dtype=out_dtype, device=a.device)
     _cuda(out, (torch.float32, torch.bfloat16), "out")
-    d = GemmDesc()
-    d.M, d.N, d.K, d.batch1, d.batch0 = M, N, K, 1, 1
-    d.A, d.lda, d.B, d.ldb = a.data_ptr(), K, b.data_ptr(), K
-    d.C, d.ldc, d.c_dtype, d.alpha = out.data_ptr(), n_out, _DT[out.dtype], alpha
-    if bias is not None:
-        d.bias, d.bias_mode = _cuda(bias, torch.float32, "bias").data_ptr(), _lib.BIAS_COL
-    d.act = {"gelu": _lib.ACT_GELU, "swiglu": _lib.ACT_SWIGLU, "silu": _lib.ACT_SILU, "glu": _lib.ACT_GLU, None: _lib.ACT_NONE}[act]
-    if res is not None:
-        d.res, d.ldres = _cuda(res, torch.float32, "res").data_ptr(), N
-    check(lib().tribe_gemm_fp8(C.byref(d), _stream()), "tribe_gemm_fp8")
+    for name, t in (("bias", bias), ("res", res)):
+        if t is not None:
+            _cuda(t, torch.float32, name)
+    _gemm(a, b, out, M=M, N=N, K=K, lda=K, ldb=K, ldc=n_out, alpha=alpha, bias=bias, act=_ACT[act], res=res, ldres=N, fp8=True)
     return out
 
 
