@@ -1061,3 +1061,11 @@ int tribe_internal_attention_fused(const uint16_t* qkv, int64_t B, int64_t T, in
   const tribe_attention_desc d = fused_desc(qkv, B, T, heads, dim_head, scale, out);
   return attention_dispatch(&d, nullptr, nullptr, 0, (void*)s);
 }
+
+// test hook (not part of include/tribe_hip.h): tribe_internal_attention_fused_qrot as the encoder calls it at dim_head 384 -- q heads of
+// `qkv` not rotated, k heads rotated, interleaved pairs, tables [T, rot_dim / 2] -- so a test can hold it against the stand-alone pass
+extern "C" int tribe_debug_attention_qrot(const uint16_t* qkv, int64_t B, int64_t T, int32_t heads, int32_t dim_head, float scale,
+                                          uint16_t* out, const float* cos_tab, const float* sin_tab, int32_t rot_dim, void* stream) {
+  TRIBE_REQUIRE(qkv && out && B > 0 && T > 0 && heads > 0, "tribe_debug_attention_qrot: null pointer or bad shape");
+  return tribe_internal_attention_fused_qrot(qkv, B, T, heads, dim_head, scale, out, cos_tab, sin_tab, rot_dim, (hipStream_t)stream);
+}

@@ -276,6 +276,11 @@ SIGNATURES = {
     "tribe_fbank_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, vp, vp, vp, i64, C.POINTER(i32), vp, sz, vp]),
 }
 
+# exports that are not part of include/tribe_hip.h: hooks that let the tests reach an internal entry point
+DEBUG_SIGNATURES = {
+    "tribe_debug_attention_qrot": (C.c_int, [vp, i64, i64, i32, i32, f32, vp, vp, vp, i32, vp]),
+}
+
 _lib = None
 
 
@@ -294,7 +299,7 @@ def lib() -> C.CDLL:
                 "(or `make -C algonauts-2025_amd/csrc`). There is no CPU / PyTorch fallback for the hot path."
             )
         handle = C.CDLL(str(path))
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in (SIGNATURES | DEBUG_SIGNATURES).items():
             fn = getattr(handle, name)  # AttributeError if the export is missing
             fn.restype = restype
             fn.argtypes = argtypes

@@ -13,6 +13,10 @@ Contents
                    (absent from /root/reference and from this image) as an
                    `nn.Module` with the library's state_dict key names.
 
+* `attention_ref` -- float64 attention forward / backward, the rounding-error
+                   bounds the GPU tests hold the kernels to, and f32 emulations
+                   of the kernels' roundings with injectable faults.
+
 Pinning status (see DESIGN.md "Oracle")
 ---------------------------------------
 * Everything that lives in the reference's own files (SubjectLayers,
