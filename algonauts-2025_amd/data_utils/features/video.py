@@ -5,8 +5,10 @@ for every 0.5 s step a clip of 64 frames covering the previous 4 s (video.py:203
 processor and `VJEPA2Model(..., output_hidden_states=True)` (video.py:247-268); the 41 hidden states are stacked and
 averaged over the 8192 tokens (video.py:228) -> `[41, 1408]` per step.  Here the encoder forward and the token mean run
 in one C call (`tribe_vjepa2_fwd`); the predictor head, whose output the reference discards, is not run.
-Frame decoding and the HF processor (resize / rescale / normalise) stay on the host (SURVEY: moviepy decode is out of
-scope); the boundary is the processor's `pixel_values_videos` f32 [B, frames, 3, H, W].
+Frame decoding stays on the host (SURVEY: moviepy decode is out of scope).  The processor (resize / crop / rescale /
+normalise) runs on the host by default, and the boundary is its `pixel_values_videos` f32 [B, frames, 3, H, W]; with
+`VJEPA2(frontend="hip")` the decoded uint8 frames are uploaded instead and `HipVideoProcessor` (`tribe_video_preprocess_fwd`,
+csrc/vidproc.hip) writes `pixel_values_videos` straight into HBM.
 """
 
 from __future__ import annotations
@@ -20,6 +22,7 @@ import torch
 
 from tribe_hip import ops
 from tribe_hip._lib import VitFp8Layer, VitLayer, Vjepa2Desc
+from tribe_hip.ops import aa_resize_taps, video_resized_size  # noqa: F401  (host helpers of the front end)
 
 from .extractor_host import ExtractorHost
 from .plugin import HbmFeaturePlugin
@@ -134,15 +137,45 @@ def default_video_processor(frames: np.ndarray, crop_size: int = 256) -> torch.T
     return ((x - mean) / std)[None]
 
 
+class HipVideoProcessor:
+    """`default_video_processor` on the GPU (`ops.video_preprocess`), usable wherever `VJEPA2.attach(processor=...)` takes a
+    processor.  Called on uint8 frames [F, H, W, 3] (numpy, host or device tensor; host frames are uploaded once, as uint8):
+    returns f32 [1, F, 3, crop, crop] on the GPU.  `batched(frames, index)` takes the DISTINCT frames of several clips and an
+    integer index [clips, F] into them and returns [clips, F, 3, crop, crop] from one launch."""
+
+    def __init__(self, crop_size: int = 256, device: str | torch.device = "cuda"):
+        self.crop_size, self.device = int(crop_size), torch.device(device)
+
+    def _upload(self, frames: tp.Any) -> torch.Tensor:
+        t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
+        if t.dtype != torch.uint8:
+            raise ValueError(f"HipVideoProcessor: frames must be uint8, got {t.dtype}")
+        return t.to(self.device).contiguous()
+
+    def __call__(self, frames: tp.Any) -> torch.Tensor:
+        dev = self._upload(frames)
+        return ops.video_preprocess(dev, np.arange(dev.shape[0]), self.crop_size)[None]
+
+    def batched(self, frames: tp.Any, index: tp.Any) -> torch.Tensor:
+        index = np.asarray(index)
+        if index.ndim != 2:
+            raise ValueError(f"HipVideoProcessor.batched: index must be [clips, frames], got {index.shape}")
+        return ops.video_preprocess(self._upload(frames), index, self.crop_size).reshape(*index.shape, 3, self.crop_size, self.crop_size)
+
+
 class VJEPA2(HbmFeaturePlugin):
     """The reference's video feature (video.py:56-236) on the HIP ViT-g forward: fields `name`, `layers`, `layer_aggregation`,
     `device`, `infra`; `prepare`, `__call__ -> Tensor[L, D, T]`, `_get_data -> [41, 1408, T_event@2Hz]` per Video event (item
     uid `filepath_offset_duration`, video.py:191-195).  Per 0.5 s step the 64 frames of the previous 4 s are decoded on the
     host (`event.read().get_frame(t)`, moviepy in the reference), processed, and the encoder forward + token mean of all
-    41 states is one C call; `clips_per_launch` steps go through the encoder together."""
+    41 states is one C call; `clips_per_launch` steps go through the encoder together.  `frontend` selects who turns the decoded
+    frames into `pixel_values_videos`: "host" (default) runs the processor per clip on the host and uploads its f32 result;
+    "hip" decodes every DISTINCT frame time of a launch group once (consecutive steps of an event whose duration is a multiple
+    of 0.5 s share most of their frames), uploads those frames as uint8 and runs `HipVideoProcessor` in one launch per group."""
 
     name: tp.Literal["VJEPA2"] = "VJEPA2"
     pretrained: str = "facebook/vjepa2-vitg-fpc64-256"    # video.py:247-254; resolved from the local HF cache only
+    frontend: tp.Literal["host", "hip"] = "host"          # a route, not a result: kept out of the class uid like `device`
     clips_per_launch: int = 4   # 37.6 ms per clip at 4, 41.3 at 2, 44.9 at 1 (profiles/r02_p_config3_e2e.txt, r02_m_extractor_bench.txt)
     _EVENT_TYPE: tp.ClassVar[str] = "Video"
     _KIND: tp.ClassVar[str] = "sampled"
@@ -151,8 +184,14 @@ class VJEPA2(HbmFeaturePlugin):
     _processor: tp.Any = pydantic.PrivateAttr(default=None)
 
     def attach(self, model: HipVJEPA2Encoder, processor: tp.Callable[[np.ndarray], torch.Tensor] | None = None) -> "VJEPA2":
+        if processor is not None and self.frontend == "hip":
+            raise ValueError('VJEPA2: frontend="hip" runs its own processor on the GPU; attach no `processor`, or use frontend="host"')
         self._model, self._processor = model, processor
         return self
+
+    @classmethod
+    def _exclude_from_cls_uid(cls) -> list[str]:
+        return super()._exclude_from_cls_uid() + ["frontend"]
 
     @property
     def model(self) -> HipVJEPA2Encoder:
@@ -170,6 +209,9 @@ class VJEPA2(HbmFeaturePlugin):
         from ..base import Frequency
 
         model = self.model
+        if self.frontend == "hip":
+            yield from self._compute_hip(events)
+            return
         process = self._processor or (lambda fr: default_video_processor(fr, model.crop))
         n_frames = model.frames
         subtimes = [k / n_frames * 4.0 for k in reversed(range(n_frames))]                  # video.py:203-205
@@ -188,3 +230,29 @@ class VJEPA2(HbmFeaturePlugin):
             if hasattr(video, "close"):
                 video.close()
             yield out.transpose(1, 2, 0)                                                    # [n_states, dim, T_event] (video.py:234)
+
+    def _compute_hip(self, events: list[tp.Any]) -> tp.Iterator[np.ndarray]:
+        """`_compute` with the processor on the GPU: per launch group the frame times of all clips are collected, each distinct
+        time (equal as Python floats, nothing looser) is decoded once, and the distinct frames go up as one uint8 tensor."""
+        from ..base import Frequency
+
+        model = self.model
+        if self._processor is not None:
+            raise ValueError('VJEPA2: frontend="hip" runs its own processor on the GPU; attach no `processor`, or use frontend="host"')
+        process = HipVideoProcessor(model.crop, model.device)
+        n_frames = model.frames
+        subtimes = [k / n_frames * 4.0 for k in reversed(range(n_frames))]                  # video.py:203-205
+        for event in events:
+            video = event.read()
+            expect = Frequency(2.0).to_ind(event.duration)
+            times = np.linspace(0, video.duration, expect + 1)[1:]                          # video.py:218
+            out = np.zeros((len(times), model.depth + 1, model.dim))
+            for k0 in range(0, len(times), self.clips_per_launch):
+                slot_of: dict[float, int] = {}                                              # distinct frame time -> row of `frames`
+                index = [[slot_of.setdefault(float(max(0, t - t2)), len(slot_of)) for t2 in subtimes] for t in times[k0:k0 + self.clips_per_launch]]
+                frames = np.array([np.asarray(video.get_frame(tt)).astype("uint8") for tt in slot_of])
+                means = model.hidden_state_means(process.batched(frames, index))            # [clips, 41, dim]
+                out[k0:k0 + len(index)] = means.cpu().numpy()
+            if hasattr(video, "close"):
+                video.close()
+            yield out.transpose(1, 2, 0)

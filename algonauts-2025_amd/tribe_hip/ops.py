@@ -949,3 +949,92 @@ def w2vbert_fbank(wavs: torch.Tensor | tp.Sequence[torch.Tensor], zscore: bool =
                                 got, ws.data_ptr(), ws.numel(), _stream()), "tribe_fbank_fwd")
     assert list(got) == lengths
     return out, lengths
+
+
+# --------------------------------------------------------------------------------------
+# V-JEPA2 video front end: decoded uint8 frames -> pixel_values_videos (csrc/vidproc.hip)
+# --------------------------------------------------------------------------------------
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def aa_resize_taps(n_in: int, n_out: int, start: int = 0, count: int | None = None) -> tuple[_np.ndarray, _np.ndarray]:
+    """The separable antialiased triangle filter of `F.interpolate(mode="bilinear", align_corners=False, antialias=True)` along
+    one axis of n_in samples resized to n_out, for output positions start .. start + count - 1: (first int32 [count], weights
+    f32 [count, taps]) with out[i] = sum_k weights[i, k] * in[first[i] + k].  With scale = n_in / n_out and support =
+    max(scale, 1), position i is centred on scale * (i + 0.5), its window is [max(0, int(centre - support + 0.5)), min(n_in,
+    int(centre + support + 0.5))), tap j weighs max(0, 1 - |(j - centre + 0.5) / max(scale, 1)|), and the weights are divided by
+    their sum: float64 throughout, rounded to f32 once.  Taps of weight exactly 0 at either end of a window are dropped (identity
+    is one tap of 1.0).  `taps` is the widest window of the table; a narrower row is padded with
+    zero weights behind, or, where that would pass the end of the axis, `first` moves down and the zeros go in front, so every row
+    has first >= 0 and first + taps <= n_in."""
+    count = n_out - start if count is None else count
+    if n_in < 1 or n_out < 1 or start < 0 or count < 1 or start + count > n_out:
+        raise ValueError(f"aa_resize_taps: positions [{start}, {start} + {count}) of an axis of {n_in} resized to {n_out}")
+    scale = n_in / n_out
+    support = max(scale, 1.0)
+    rows = []
+    for i in range(start, start + count):
+        centre = scale * (i + 0.5)
+        lo, hi = max(0, int(centre - support + 0.5)), min(n_in, int(centre + support + 0.5))
+        w = _np.maximum(0.0, 1.0 - _np.abs((_np.arange(lo, hi, dtype=_np.float64) - centre + 0.5) / support))
+        keep = _np.flatnonzero(w)                                   # the window's end positions may weigh exactly 0 (always, at scale <= 1)
+        rows.append((lo + int(keep[0]), (w / w.sum())[keep[0]:keep[-1] + 1]))
+    taps = max(len(w) for _, w in rows)
+    first = _np.empty(count, _np.int32)
+    weights = _np.zeros((count, taps), _np.float64)
+    for r, (lo, w) in enumerate(rows):
+        first[r] = min(lo, n_in - taps)
+        weights[r, lo - first[r]:lo - first[r] + len(w)] = w
+    return first, weights.astype(_np.float32)
+
+
+def video_resized_size(H: int, W: int, crop: int) -> tuple[int, int]:
+    """The size `default_video_processor` resizes an H x W frame to: shortest edge int(crop * 256 / 224), aspect kept."""
+    short = int(crop * 256 / 224)
+    scale = short / min(H, W)
+    return max(short, int(round(H * scale))), max(short, int(round(W * scale)))
+
+
+_VIDEO_TABLES: dict[tuple[int, int, int], tuple[tp.Any, ...]] = {}
+
+
+def _video_tables(H: int, W: int, crop: int) -> tuple[tp.Any, ...]:
+    key = (H, W, crop)
+    if key not in _VIDEO_TABLES:
+        nh, nw = video_resized_size(H, W, crop)
+        first_h, w_h = aa_resize_taps(H, nh, (nh - crop) // 2, crop)
+        first_w, w_w = aa_resize_taps(W, nw, (nw - crop) // 2, crop)
+        _VIDEO_TABLES[key] = (nh, nw, first_h, _np.ascontiguousarray(w_h), first_w, _np.ascontiguousarray(w_w))
+    return _VIDEO_TABLES[key]
+
+
+def video_preprocess(frames_u8: torch.Tensor, src_index: tp.Any, crop: int) -> torch.Tensor:
+    """What `data_utils.features.video.default_video_processor` computes, on the GPU: frames_u8 uint8 [n_src, H, W, 3] (device,
+    contiguous) are resized (antialiased bilinear, shortest edge to int(crop * 256 / 224)), centre-cropped, divided by 255 and
+    ImageNet-normalised.  src_index (ints, any shape, flattened) names the source frame of every output slot, so a frame several
+    clips share is stored once: -> f32 [n_out, 3, crop, crop] from one launch, each slot the same bits whatever else is in the batch."""
+    _cuda(frames_u8, None, "frames_u8", contiguous=False)
+    if frames_u8.dtype != torch.uint8:
+        raise ValueError(f"video_preprocess: frames must be uint8, got {frames_u8.dtype}")
+    if frames_u8.ndim != 4 or frames_u8.shape[-1] != 3 or frames_u8.shape[0] < 1:
+        raise ValueError(f"video_preprocess: frames must be [n_src, H, W, 3], got {tuple(frames_u8.shape)}")
+    if not frames_u8.is_contiguous():
+        raise ValueError("video_preprocess: frames must be contiguous")
+    src = _np.ascontiguousarray(_np.asarray(src_index.cpu() if isinstance(src_index, torch.Tensor) else src_index).reshape(-1))
+    if src.size < 1 or src.dtype.kind not in "iu":
+        raise ValueError("video_preprocess: src_index must hold at least one integer")
+    n_src, H, W = (int(v) for v in frames_u8.shape[:3])
+    if int(src.min()) < 0 or int(src.max()) >= n_src:
+        raise ValueError(f"video_preprocess: src_index must lie in [0, {n_src}), got [{int(src.min())}, {int(src.max())}]")
+    src = src.astype(_np.int32)
+    crop = int(crop)
+    if crop < 1:
+        raise ValueError(f"video_preprocess: crop {crop}")
+    nh, nw, first_h, w_h, first_w, w_w = _video_tables(H, W, crop)
+    mean, std = (C.c_float * 3)(*IMAGENET_MEAN), (C.c_float * 3)(*IMAGENET_STD)
+    out = torch.empty(src.size, 3, crop, crop, dtype=torch.float32, device=frames_u8.device)
+    ws = workspace(lib().tribe_video_preprocess_workspace_bytes(src.size, crop, w_h.shape[1], w_w.shape[1]), frames_u8.device, tag="vidproc")
+    check(lib().tribe_video_preprocess_fwd(frames_u8.data_ptr(), n_src, H, W, src.ctypes.data, src.size, nh, nw, crop, first_h.ctypes.data,
+                                           w_h.ctypes.data, w_h.shape[1], first_w.ctypes.data, w_w.ctypes.data, w_w.shape[1], mean, std,
+                                           out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "tribe_video_preprocess_fwd")
+    return out

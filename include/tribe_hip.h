@@ -596,6 +596,27 @@ int tribe_fbank_fwd(const float* const* wavs_host, const int64_t* n_host, int32_
                     const float* window, const float* mel, float* out, int64_t T_max, int32_t* lengths_host, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- video front end: decoded uint8 frames -> V-JEPA2 pixel_values_videos (data_utils/features/video.py `default_video_processor`) ----
+ * Replaces the host processor in front of the ViT: antialiased bilinear resize (torch's `interpolate(mode="bilinear",
+ * antialias=True)`: a separable triangle filter) of frames to resized_h x resized_w, a crop window of crop x crop, / 255,
+ * (v - mean[c]) / std[c].  Only the crop window is computed.  Along an axis, output position i of the window is
+ * sum_k w[i][k] * in[first[i] + k], an f32 fma chain in tap order, W pass first; `data_utils.features.video.aa_resize_taps`
+ * builds the tables.  frames: DEVICE uint8 [n_src, H, W, 3], contiguous (no row alignment is assumed).  Everything else
+ * that is indexed arrives in HOST arrays and is checked before anything is launched: src_host int32 [n_out], the source frame
+ * of every output slot, each in [0, n_src); first_h_host int32 [crop] / w_h_host f32 [crop, taps_h] with 0 <= first and
+ * first + taps_h <= H, non-decreasing; first_w_host / w_w_host / taps_w likewise against W; crop <= resized_h, resized_w;
+ * mean_host, std_host f32 [3], std > 0; taps_h <= 64 (a tile's input rows are staged through LDS).  A violation returns < 0.
+ * The tables are copied into the workspace in-stream; the host arrays may be reused when the call returns.
+ * out: DEVICE f32 [n_out, 3, crop, crop] (= [clips, frames, 3, crop, crop] of tribe_vjepa2_fwd's `pixels`).  One launch; a
+ * slot's values depend on its source frame only and are the same bits on every call and in every batch.
+ * tribe_video_preprocess_workspace_bytes returns 0 for arguments the forward refuses. */
+size_t tribe_video_preprocess_workspace_bytes(int64_t n_out, int32_t crop, int32_t taps_h, int32_t taps_w);
+int tribe_video_preprocess_fwd(const uint8_t* frames, int64_t n_src, int32_t H, int32_t W, const int32_t* src_host, int64_t n_out,
+                               int32_t resized_h, int32_t resized_w, int32_t crop, const int32_t* first_h_host, const float* w_h_host,
+                               int32_t taps_h, const int32_t* first_w_host, const float* w_w_host, int32_t taps_w,
+                               const float* mean_host, const float* std_host, float* out, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 /* ---- steps after the model ------------------------------------------------------------ */
 /* out[z, c, r] = in[z, r, c], f32: predictions [B, V, T'] -> [B, T', V] rows for the submission writer
  * (`pred = y_pred[i].cpu().numpy().T`, algonauts2025/callbacks.py:63-64), one launch + one D2H copy per batch. */
