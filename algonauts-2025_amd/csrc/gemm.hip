@@ -100,6 +100,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_256x256x64(const tribe_gemm_de
   constexpr int WN = 16 * NB;                      // columns per wave
   constexpr int VM_STEADY = NB == 4 ? TRIBE_GEMM_VM_STEADY : 4 + NB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+#ifdef TRIBE_GEMM_STAMPS
+  unsigned long long ts_entry = 0, ts_loop = 0, ts_end = 0;
+  TRIBE_STAMP(ts_entry);
+#endif
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..7
@@ -358,6 +362,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_256x256x64(const tribe_gemm_de
   if (wr == 1) __builtin_amdgcn_s_setprio(1);
 #endif
 
+  TRIBE_STAMP(ts_loop);
   for (int t = 0; t < nk; ++t) {
     const int cur = t & 1;
     const char* base = smem + cur * BUF_BYTES;
@@ -389,6 +394,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_256x256x64(const tribe_gemm_de
   }
   if (wr == 0) __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_s_setprio(0);
+  TRIBE_STAMP(ts_end);
 #ifdef TRIBE_GEMM_STAMPS
   if (g.gadd == nullptr && g.gadd_index != nullptr && lane == 0 && blockIdx.y == 0) {
     unsigned long long* dbg = (unsigned long long*)g.gadd_index + ((size_t)blockIdx.x * 8 + wave) * 8;
@@ -415,15 +421,31 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_256x256x64(const tribe_gemm_de
       return;
     }
   }
-  if (epilogue_fast_ok<(ROLE == TRIBE_ROLE_EXT)>(g, ctx) && n0 + BN <= g.N) {
+  // The four encoder roles: the epilogue compiled for exactly their operator set, and nothing else -- the launcher (role8_ok) sends these
+  // instantiations only descriptors that carry it (un-batched, alpha == 1, N a multiple of the tile width, 16-byte operands); every other
+  // launch of such a role runs under the GENERIC symbol.
+  constexpr bool ROLE_EPI = TACC && (ROLE == TRIBE_ROLE_QKV || ROLE == TRIBE_ROLE_FF1 || ROLE == TRIBE_ROLE_OUT_PROJ || ROLE == TRIBE_ROLE_FF2);
+  if constexpr (ROLE_EPI) {
+    epilogue_role<OUT_BF16, ROLE, 8, NB, TACC>(g, acc, m0 + wr * 128, n0 + wc * WN, lane, smem + wave * (4 * NB * 1024));
+  } else if (epilogue_fast_ok<(ROLE == TRIBE_ROLE_EXT)>(g, ctx) && n0 + BN <= g.N) {
     // nothing inside the sub-tile loop waits on memory (gemm_common.h); the staging buffers are idle by now
     epilogue_fast<OUT_BF16, 8, NB, (ROLE == TRIBE_ROLE_EXT), TACC>(g, ctx, acc, m0 + wr * 128, n0 + wc * WN, lane, smem + wave * (4 * NB * 1024));
-    return;
+  } else {
+    static_for<8 * NB>([&](auto t) {
+      constexpr int i = decltype(t)::value / NB, j = decltype(t)::value % NB;
+      epilogue_tile16<OUT_BF16, (ROLE == TRIBE_ROLE_EXT), TACC>(g, ctx, acc[i][j], m0 + wr * 128 + i * 16, n0 + wc * WN + j * 16, lane);
+    });
   }
-  static_for<8 * NB>([&](auto t) {
-    constexpr int i = decltype(t)::value / NB, j = decltype(t)::value % NB;
-    epilogue_tile16<OUT_BF16, (ROLE == TRIBE_ROLE_EXT), TACC>(g, ctx, acc[i][j], m0 + wr * 128 + i * 16, n0 + wc * WN + j * 16, lane);
-  });
+#ifdef TRIBE_GEMM_STAMPS
+  // slots 5 .. 7: kernel entry -> first K-loop iteration; end of the K loop -> last store issued; -> every store retired (wave end)
+  TRIBE_STAMP(ts1);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  TRIBE_STAMP(ts2);
+  if (g.gadd == nullptr && g.gadd_index != nullptr && lane == 0 && blockIdx.y == 0) {
+    unsigned long long* dbg = (unsigned long long*)g.gadd_index + ((size_t)blockIdx.x * 8 + wave) * 8;
+    dbg[5] = ts_loop - ts_entry; dbg[6] = ts1 - ts_end; dbg[7] = ts2 - ts_end;
+  }
+#endif
 }
 
 // Second launch of a stream-K GEMM: workgroup t sums the parts of tile tiles_dp + t in worker order (first parts and second parts of the runs
@@ -1150,7 +1172,8 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_4w256(const tribe_gemm_desc g,
 // Launch tables.  gemm.hip is compiled in four parts (Makefile: -DTRIBE_GEMM_PART=0 .. 3 -> gemm.o, gemm_p1.o, gemm_p2.o, gemm_p3.o) so that
 // the instantiations build side by side: part 0 = the C entry points + the 8-wave 256 x 256 kernel (and its transposed-operand form),
 // part 1 = the 256 x 192 kernel, part 2 = the two 128 x 128 kernels, part 3 = the 4-wave 256 x 256 kernel.  A build without the macro compiles everything in one unit.
-// ROLE only gives each call site of the path its own kernel symbol, so that rocprofv3 --stats reports per-operator rows.
+// ROLE gives each call site of the path its own kernel symbol, so that rocprofv3 --stats reports per-operator rows; in the 8-wave NT kernel the
+// four encoder roles (QKV, FF1, OUT_PROJ, FF2) also compile the epilogue of exactly their operator set (epilogue_role, launcher: role8_ok).
 // ---------------------------------------------------------------------------------------------
 #ifndef TRIBE_GEMM_PART
 #define TRIBE_GEMM_PART -1
@@ -1373,6 +1396,27 @@ static bool w4_role_ok(const tribe_gemm_desc* d) {
   }
   return (int64_t)255 * (d->lda > d->ldb ? d->lda : d->ldb) * 2 + 8192 < (1ll << 32);   // 32-bit per-lane offsets of the LDS-DMA pieces
 }
+// true when the descriptor carries exactly the operator set epilogue_role compiles for its role in the 8-wave NT kernel with tiles `bn` wide:
+// un-batched, alpha == 1, no tile crossing N, and every operand as aligned as epilogue_fast's vector accesses need (make_epi_ctx).
+// [row_scale] of QKV / FF1 and [res_scale], [c_bf16], [row_sumsq] of out-proj / FF2 may be absent (first layer, last layer, unfused norm).
+static bool role8_ok(const tribe_gemm_desc* d, int bn) {
+  const bool res_role = d->role == TRIBE_ROLE_OUT_PROJ || d->role == TRIBE_ROLE_FF2;
+  const bool bf_role = d->role == TRIBE_ROLE_QKV || d->role == TRIBE_ROLE_FF1;
+  if (!res_role && !bf_role) return false;
+  if (d->batch1 * d->batch0 != 1 || d->trans_ab || d->gather1 || d->N % bn != 0 || d->alpha != 1.0f || d->rowadd || d->gadd || d->aux) return false;
+  if (d->c_dtype != (bf_role ? TRIBE_BF16 : TRIBE_F32) || d->ldc % 4 != 0 || ((uintptr_t)d->C % (bf_role ? 8 : 16)) != 0) return false;
+  const bool wants_bias = d->role == TRIBE_ROLE_FF1 || d->role == TRIBE_ROLE_FF2;
+  if (wants_bias ? (d->bias_mode != TRIBE_BIAS_COL || !d->bias || ((uintptr_t)d->bias % 16) != 0) : d->bias_mode != TRIBE_BIAS_NONE) return false;
+  if (d->act != (d->role == TRIBE_ROLE_FF1 ? TRIBE_ACT_GELU : TRIBE_ACT_NONE)) return false;
+  if (res_role) {
+    if (!d->res || d->ldres % 4 != 0 || ((uintptr_t)d->res % 16) != 0 || d->row_scale) return false;
+    if (d->res_scale && ((uintptr_t)d->res_scale % 16) != 0) return false;
+    if (d->c_bf16 && (d->ld_c_bf16 % 4 != 0 || ((uintptr_t)d->c_bf16 % 8) != 0)) return false;
+  } else {
+    if (d->res || d->res_scale || d->c_bf16 || d->row_sumsq) return false;
+  }
+  return true;
+}
 static GemmPlan gemm_plan(const tribe_gemm_desc* d) {
   const int64_t nz = d->batch1 * d->batch0;
   auto tiles = [&](int64_t bm, int64_t bn) { return ((d->M + bm - 1) / bm) * ((d->N + bn - 1) / bn) * nz; };
@@ -1389,7 +1433,7 @@ static GemmPlan gemm_plan(const tribe_gemm_desc* d) {
   if (use_big && t128 >= 512 && (double)t128 * 128 * 128 * 1.25 <= (double)t256 * 256 * 256) use_big = 0;
   if (fused_norm && d->N % 128 != 0) use_big = 1;   // (the launcher then reports the N it needs)
   if (d->tile_hint == 1 || d->tile_hint == 3) use_big = 0;
-  if (d->tile_hint == 2 || d->tile_hint == 4 || d->tile_hint == 5) use_big = 1;
+  if (d->tile_hint == 2 || d->tile_hint == 4 || d->tile_hint == 5 || d->tile_hint == 6) use_big = 1;
   if (d->trans_ab) return {KIND_BIG, 256, 256, 64};
   if (!use_big) {
     // one workgroup per CU or fewer: the ring kernel (three K-tiles in flight); more: the double-buffered kernel, whose two or three
@@ -1416,6 +1460,7 @@ static GemmPlan gemm_plan(const tribe_gemm_desc* d) {
   // instead of 3/4 of it).  A 192-wide tile costs ~0.78 of a 256-wide one; large grids keep 256^2 (higher operand reuse).
   int bn = 256;
   if (d->tile_hint == 4) bn = 192;
+  else if (d->tile_hint == 6) bn = (d->N % 256 != 0 && d->N % 192 == 0) ? 192 : 256;   // the width whose tiles stay inside N (A/B against the role kernels)
   else if (d->tile_hint == 0 && d->N % 192 == 0 && t256 <= 2048) {
     const int64_t t192 = tiles(256, 192);
     const double cost4 = (double)((t256 + 255) / 256), cost3 = (double)((t192 + 255) / 256) * 0.78;
@@ -1432,6 +1477,14 @@ static GemmPlan gemm_plan(const tribe_gemm_desc* d) {
   const bool w4_default = TRIBE_GEMM_4W_DEFAULT && d->tile_hint == 0 && (d->role == TRIBE_ROLE_QKV || d->role == TRIBE_ROLE_FF1);
   if (bn == 256 && (d->tile_hint == 5 || w4_default) && w4_role_ok(d)) return {KIND_BIG4W, 256, 256, 64};
   return {KIND_BIG, 256, bn, bn / 4};
+}
+// the 8-wave NT kernel with the role-compiled epilogue (tile_hint 6 = the same tiles with the generic epilogue, for A/B runs and tests).
+// Default per role by the same-box measurements of DESIGN 4.1b (B = 64, parent -> role kernel): QKV 2.774 -> 2.737 ms, FF1 3.881 -> 3.704 ms,
+// out-proj 1.212 -> 1.182 ms take it; FF2 (3.795 -> 3.782 ms, 3813 -> 3811 us in the kernel trace: inside the run-to-run spread -- its K = 12288
+// loop is 4x as long and its epilogue waits on the residual, not on instructions) keeps the generic epilogue unless tile_hint 2 / 4 asks.
+static bool takes_role_epilogue(const tribe_gemm_desc* d, const GemmPlan& plan) {
+  if (plan.kind != KIND_BIG || d->trans_ab || d->tile_hint == 6 || !role8_ok(d, plan.bn)) return false;
+  return d->role != TRIBE_ROLE_FF2 || d->tile_hint == 2 || d->tile_hint == 4;
 }
 }  // namespace tribe_gemm_detail
 
@@ -1584,6 +1637,9 @@ extern "C" int tribe_gemm_bf16(const tribe_gemm_desc* d, void* stream) {
     }
   }
   using namespace tribe_gemm_detail;
+  // The 8-wave kernels of QKV / FF1 / out-proj / FF2 carry ONLY the epilogue of their role's operator set (epilogue_role): a launch of such a
+  // role with any other descriptor -- or with tile_hint 6, the A/B switch -- runs the generic epilogue under the GENERIC symbol.
+  if (plan.kind == KIND_BIG && (pair == 5 || pair == 8 || pair == 9 || pair == 10) && !takes_role_epilogue(d, plan)) pair = bf ? 0 : 1;
   if (plan.kind == KIND_BIG4W) launch_4w(pair, grid, s, d, (int)tiles_m, (int)tiles_n);
   else if (plan.kind == KIND_BIG && plan.bn == 192) launch_big3(pair, grid, s, d, (int)tiles_m, (int)tiles_n);
   else if (plan.kind == KIND_BIG) launch_big4(pair, grid, s, d, (int)tiles_m, (int)tiles_n);
@@ -1630,5 +1686,14 @@ extern "C" int tribe_gemm_sumsq_slots(const tribe_gemm_desc* d) {
   TRIBE_REQUIRE(d != nullptr && d->M > 0 && d->N > 0 && d->K > 0 && d->batch1 > 0 && d->batch0 > 0, "tribe_gemm_sumsq_slots: bad descriptor");
   const tribe_gemm_detail::GemmPlan plan = tribe_gemm_detail::gemm_plan(d);
   return (int)(d->N / plan.sumsq_cols);
+}
+
+// which epilogue the launch of `desc` runs: 0 = the generic one (operators decided at run time), 1 = the 8-wave kernel's role-compiled one
+// (epilogue_role), 2 = the one-wave-per-SIMD kernel's (epilogue_w4).  Host-side only: no GPU call.
+extern "C" int tribe_gemm_epilogue_path(const tribe_gemm_desc* d) {
+  TRIBE_REQUIRE(d != nullptr && d->M > 0 && d->N > 0 && d->K > 0 && d->batch1 > 0 && d->batch0 > 0, "tribe_gemm_epilogue_path: bad descriptor");
+  const tribe_gemm_detail::GemmPlan plan = tribe_gemm_detail::gemm_plan(d);
+  if (plan.kind == tribe_gemm_detail::KIND_BIG4W) return 2;
+  return tribe_gemm_detail::takes_role_epilogue(d, plan) ? 1 : 0;
 }
 #endif  // part 0

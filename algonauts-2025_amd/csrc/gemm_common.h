@@ -487,6 +487,132 @@ __device__ __forceinline__ void epilogue_fast(const tribe_gemm_desc& g, const Ep
   });
 }
 
+// a product the compiler may not contract with the addition that follows it (epilogue_fast scales and adds in separate basic blocks: two roundings)
+__device__ __forceinline__ float mul_unfused(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// epilogue_fast<.., TACC = 1> with the operator set of one encoder GEMM fixed at COMPILE time (the 8-wave NT kernel; the launcher's
+// role8_ok sends a descriptor here only when it carries exactly this set, un-batched, alpha == 1, tiles inside N, 16-byte operands):
+//   QKV       [row_scale] -> bf16                              FF1   [row_scale] + column bias + gelu_poly2 -> bf16
+//   OUT_PROJ  res * [res_scale] (LDS slot) -> f32 [+ c_bf16] [+ row_sumsq]      FF2   column bias + the OUT_PROJ set
+// ([..] = may be absent: a factor of exactly 1 / a wave-uniform skip.)  Same rounds of 16 sub-tiles, same hoisted operands, same order of
+// floating-point operations per element -- outputs are bit-identical to epilogue_fast's -- but no test of an operator the role lacks,
+// no multiplication by alpha, and every store address is a per-lane row pointer stepped by 16 rows (the column offset of sub-tile j is an
+// immediate) instead of a 64-bit c_off + row * ldc + col rebuilt per store.  23 (QKV) to 63 (FF1) instructions per sub-tile.
+template <int OUT_BF16, int ROLE, int NI, int NJ, int TACC>
+__device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t (&acc)[NI][NJ], int64_t mw, int64_t nw, int lane, char* lds_wave) {
+  constexpr bool BIAS = ROLE == TRIBE_ROLE_FF1 || ROLE == TRIBE_ROLE_FF2;
+  constexpr bool GELU = ROLE == TRIBE_ROLE_FF1;
+  constexpr bool RES = ROLE == TRIBE_ROLE_OUT_PROJ || ROLE == TRIBE_ROLE_FF2;
+  constexpr int RI = 4, ROUNDS = NI / RI;
+  static_assert(TACC == 1 && NI % RI == 0 && NJ >= 1 && NJ <= 4, "transposed accumulators, rounds of 4 sub-tile rows");
+  static_assert(OUT_BF16 == (RES ? 0 : 1), "QKV / FF1 write bf16, out-proj / FF2 the f32 residual stream");
+  const int tq = lane >> 4;
+  const int64_t row0 = mw + (lane & 15);                                   // + 16 i
+  const int64_t col0 = nw + 4 * ((tq & 1) * 2 + (tq >> 1));                // + 16 j
+  const int64_t colp = nw + 16 * (lane >> 5) + 8 * (tq & 1);               // first of the 8 columns a paired bf16 store writes (+ 16 j, j even)
+  const int64_t left = g.M - row0;
+  const int rows_left = left >= 16 * NI ? 16 * NI : (left > 0 ? (int)left : 0);   // sub-tile row i of this lane is inside M iff 16 i < rows_left
+  const bool has_rs = !RES && g.row_scale != nullptr, has_rsc = RES && g.res_scale != nullptr;
+  const bool has_cb = RES && g.c_bf16 != nullptr, has_ssq = RES && g.row_sumsq != nullptr;
+  float4 bcol[NJ], rsc[NJ];
+  static_for<NJ>([&](auto jt) {
+    constexpr int j = decltype(jt)::value;
+    if constexpr (BIAS) bcol[j] = *(const float4*)(g.bias + col0 + j * 16);
+    if constexpr (RES) rsc[j] = has_rsc ? *(const float4*)(g.res_scale + col0 + j * 16) : make_float4(1.f, 1.f, 1.f, 1.f);
+  });
+  // row pointers of sub-tile row 0, advanced by 16 rows after every sub-tile row
+  unsigned short* c16 = OUT_BF16 ? (unsigned short*)g.C + row0 * g.ldc : (has_cb ? g.c_bf16 + row0 * g.ld_c_bf16 : nullptr);   // the bf16 rows
+  const int64_t step16 = 16 * (OUT_BF16 ? g.ldc : g.ld_c_bf16);
+  float* c32 = RES ? (float*)g.C + row0 * g.ldc + col0 : nullptr;
+  const float* rsrc = RES ? g.res + row0 * g.ldres + col0 : nullptr;
+  static_for<ROUNDS>([&](auto rt) {
+    constexpr int round = decltype(rt)::value;
+    float srow[RI], ssq[RI];
+    static_for<RI>([&](auto it) {
+      constexpr int i4 = decltype(it)::value, i = round * RI + i4;
+      ssq[i4] = 0.f;
+      srow[i4] = (has_rs && i * 16 < rows_left) ? g.row_scale[row0 + i * 16] : 1.0f;
+    });
+    if constexpr (RES) {
+      static_for<RI>([&](auto it) {
+        constexpr int i4 = decltype(it)::value, i = round * RI + i4;
+        if (i * 16 < rows_left) {   // rows past M (bottom tile row): the lane neither fetches nor stores
+          static_for<NJ>([&](auto jt) {
+            constexpr int j = decltype(jt)::value;
+            __builtin_amdgcn_global_load_lds((gptr_t)(rsrc + j * 16), (lptr_t)(lds_wave + (i4 * NJ + j) * 1024), 16, 0, 0);
+          });
+        }
+        rsrc += 16 * g.ldres;
+      });
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA's LDS writes are invisible to the compiler's own counters
+    }
+    uint2 pend = make_uint2(0u, 0u);   // the packed bf16 quad of a pair's first sub-tile
+    static_for<RI * NJ>([&](auto st) {
+      constexpr int s = decltype(st)::value, i4 = s / NJ, i = round * RI + i4, j = s % NJ;
+      const bool live = i * 16 < rows_left;   // (every lane stays for the half-wave exchanges of the paired stores; loads and stores are guarded)
+      float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+      if constexpr (!RES) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = mul_unfused(v[k], srow[i4]);
+      }
+      if constexpr (BIAS) { v[0] += bcol[j].x; v[1] += bcol[j].y; v[2] += bcol[j].z; v[3] += bcol[j].w; }
+      if constexpr (GELU) {
+        const f32x2_t lo = gelu_poly2(f32x2_t{v[0], v[1]}), hi = gelu_poly2(f32x2_t{v[2], v[3]});
+        v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+      }
+      if constexpr (RES) {
+        const float4 r = *(const float4*)(lds_wave + s * 1024 + lane * 16);
+        v[0] += r.x * rsc[j].x; v[1] += r.y * rsc[j].y; v[2] += r.z * rsc[j].z; v[3] += r.w * rsc[j].w;
+      }
+      // a bf16 row of 4 values: alone (8 bytes), or -- sub-tiles in pairs -- merged with the partner half-wave's into 16 bytes
+      auto store_bf16 = [&]() {
+        u16x4_t o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = f32_to_bf16(v[k]);
+        constexpr bool paired = NJ % 2 == 0 || j + 1 < NJ || (j & 1);
+        if constexpr (!paired) {
+          if (live) *(u16x4_t*)(c16 + col0 + j * 16) = o;
+        } else {
+          const uint2 pk = __builtin_bit_cast(uint2, o);
+          if constexpr ((j & 1) == 0) {
+            pend = pk;
+          } else {
+            const auto sx = __builtin_amdgcn_permlane32_swap(pend.x, pk.x, false, false);
+            const auto sy = __builtin_amdgcn_permlane32_swap(pend.y, pk.y, false, false);
+            if (live) *(uint4*)(c16 + colp + (j - 1) * 16) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+          }
+        }
+      };
+      if constexpr (OUT_BF16) {
+        store_bf16();
+      } else {
+        if (live) *(float4*)(c32 + j * 16) = make_float4(v[0], v[1], v[2], v[3]);
+        if (has_cb) store_bf16();   // the next GEMM's A operand, un-normalised (its ScaleNorm factor rides in that GEMM's row_scale)
+        if (has_ssq && live) ssq[i4] += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+      }
+      if constexpr (j == NJ - 1) {   // next sub-tile row
+        c16 += step16;
+        if constexpr (RES) c32 += 16 * g.ldc;
+      }
+    });
+    if constexpr (RES) {
+      if (has_ssq) {
+        // the 4 NJ values a lane holds of row i (NJ sub-tiles x 4 columns) + the three other lanes of that row -> one slot per wave
+        static_for<RI>([&](auto it) {
+          constexpr int i4 = decltype(it)::value, i = round * RI + i4;
+          float t = ssq[i4];
+          t += __shfl_xor(t, 16, 64);   // the four lanes that share a row
+          t += __shfl_xor(t, 32, 64);
+          if (lane < 16 && i * 16 < rows_left) g.row_sumsq[(row0 + i * 16) * g.ld_row_sumsq + (int64_t)((unsigned)nw / (unsigned)(16 * NJ))] = t;
+        });
+      }
+    }
+  });
+}
+
 // true when epilogue_fast covers this launch's operators; the caller checks that the tile does not cross N (rows past M
 // are masked per lane, so the bottom tile row of an M that is not a multiple of the tile still takes the fast path)
 template <int EXT>

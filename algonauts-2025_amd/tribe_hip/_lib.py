@@ -193,6 +193,7 @@ SIGNATURES = {
     "tribe_last_error": (C.c_char_p, []),
     "tribe_gemm_bf16": (C.c_int, [C.POINTER(GemmDesc), vp]),
     "tribe_gemm_sumsq_slots": (C.c_int, [C.POINTER(GemmDesc)]),
+    "tribe_gemm_epilogue_path": (C.c_int, [C.POINTER(GemmDesc)]),
     "tribe_gemm_stream_k_workspace_bytes": (i64, [C.POINTER(GemmDesc)]),
     "tribe_gemm_stream_k_plan": (C.c_int, [i32, i32, C.POINTER(i32)]),
     "tribe_prof_begin": (C.c_int, [i32]),

@@ -96,7 +96,8 @@ typedef struct tribe_gemm_desc {
   void* aux; int64_t ld_aux;
   int32_t gather_b;        /* gather1 also replaces b1 for the B operand */
   int32_t role;            /* enum tribe_gemm_role */
-  int32_t tile_hint;       /* 0 = automatic; tests / tuning: 1 = 128x128 double-buffered, 2 = 256x256, 3 = 128x128 ring, 4 = 256x192, 5 = 256x256 one-wave-per-SIMD */
+  int32_t tile_hint;       /* 0 = automatic; tests / tuning: 1 = 128x128 double-buffered, 2 = 256x256, 3 = 128x128 ring, 4 = 256x192, 5 = 256x256 one-wave-per-SIMD,
+                            * 6 = 8-wave 256-row tiles (256x192 when only that width divides N) with the GENERIC epilogue even where the role-compiled one applies (A/B runs, tests) */
   /* 1 = the operands are given TRANSPOSED: A is At [K, M] (lda >= M), B is Bt [K, N] (ldb >= N), C[m][n] = sum_k At[k][m] Bt[k][n] --
    * the weight gradient dW = dY^T X straight from the row-major dY [tokens, N_out] and X [tokens, K_in] the forward produced, without
    * the explicit transposes (torch.nn.functional.linear's backward in the reference).  M, N multiples of 8; plain epilogue only. */
@@ -127,6 +128,10 @@ int tribe_gemm_bf16(const tribe_gemm_desc* desc, void* stream);
 /* number of row_sumsq slots per row the launch of `desc` writes (N / 64, or N / 48 when the launch gets 256 x 192 tiles); < 0 on a bad
  * descriptor.  Depends on M, N, K, the batch counts, tile_hint and the fused-norm operands only. */
 int tribe_gemm_sumsq_slots(const tribe_gemm_desc* desc);
+/* which epilogue the launch of `desc` runs (host-side, no GPU call): 0 = generic (operators decided at run time), 1 = the 8-wave 256-row
+ * kernel's epilogue compiled for the operator set of desc->role (QKV / FF1 / OUT_PROJ / FF2 with exactly their model operators, un-batched,
+ * alpha == 1, N a multiple of the tile width, 16-byte operands; FF2 only under tile_hint 2 / 4), 2 = the one-wave-per-SIMD kernel's (tile_hint 5); < 0 on a bad descriptor */
+int tribe_gemm_epilogue_path(const tribe_gemm_desc* desc);
 /* bytes of desc->stream_k_ws this launch needs: 0 when it would not be split (stream_k clear, not trans_ab, or no partial round worth cutting) */
 int64_t tribe_gemm_stream_k_workspace_bytes(const tribe_gemm_desc* desc);
 /* The stream-K schedule of a launch with `tiles` output tiles of `nk` K-steps on this device (host-only, for inspection and tests):
