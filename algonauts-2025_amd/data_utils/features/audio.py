@@ -3,7 +3,8 @@
 Mirror of the reference plugin `Wav2VecBert` (/root/reference/data_utils/data_utils/features/audio.py:27-263): a 30-60 s
 waveform chunk is resampled to 16 kHz, z-scored and turned into 160-dim filterbank features by the HF SeamlessM4T
 feature extractor (audio.py:222-234; on the host by default, or on the GPU by `HipFbank` = `tribe_fbank_fwd` with
-`frontend="hip"`; resampling and soundfile IO stay on the host, like the reference's julius);
+`frontend="hip"`; resampling is scipy's on the host by default, or the reference's julius filter on the GPU by
+`tribe_resample_frac_fwd` with `resampler="hip"`; soundfile IO stays on the host);
 `Wav2Vec2BertModel(features, output_hidden_states=True)` (audio.py:253-263) yields 25 hidden states `[T@50Hz, 1024]`,
 which are resampled to 2 Hz by nearest-neighbour `F.interpolate` (audio.py:163-171) -> `[25, 1024, 2*duration]`.
 
@@ -23,7 +24,8 @@ import torch
 
 from tribe_hip import ops
 from tribe_hip._lib import ConformerFp8Layer, ConformerLayer, W2vBertDesc
-from tribe_hip.ops import fbank_frame_count, kaldi_mel_filters, povey_window  # noqa: F401  (host helpers of the front end)
+from tribe_hip.ops import (fbank_frame_count, julius_resample_kernels, kaldi_mel_filters, povey_window,  # noqa: F401  (host helpers
+                           resample_output_length)                                                       # of the front end)
 
 from .extractor_host import ExtractorHost
 from .plugin import HbmFeaturePlugin
@@ -150,8 +152,13 @@ class HipFbank:
 class Wav2VecBert(HbmFeaturePlugin):
     """The reference's audio feature (audio.py:27-263) on the HIP conformer forward: fields `name`, `layers`,
     `layer_aggregation`, `device`, `infra`; `prepare`, `__call__ -> Tensor[L, D, T]`, `_get_data -> [25, 1024, T_event@2Hz]`
-    per Sound event (item uid `filepath_offset_duration`, audio.py:145-149).  Waveform IO (`event.read()`) and resampling stay
-    on the host as in the reference (third-party there too).  `frontend` selects who turns the 16 kHz waveform into
+    per Sound event (item uid `filepath_offset_duration`, audio.py:145-149).  Waveform IO (`event.read()`) stays on the host as in
+    the reference (third-party there too).  `resampler` selects who brings the waveform to 16 kHz: "scipy" (default) is
+    `scipy.signal.resample_poly` on the host, as this build always did; "hip" uploads the native-rate waveform once and runs the
+    reference's own filter, `julius.resample.ResampleFrac` per channel (audio.py:129-138), on the GPU (`ops.resample_frac`).  The
+    two filters differ, so unlike `frontend` this field changes the result: it stays in the class uid and marks the item uid
+    (`..._julius`).  julius is not installed here; its filter is restated from its published source, not executed.
+    `frontend` selects who turns the 16 kHz waveform into
     `input_features`: "hf" (default) is the reference's route -- `_preprocess_wav` in torch and the HF filterbank extractor on
     the host, then one upload of the features; "hip" uploads the waveform once and runs the channel mean, the z-score and the
     whole filterbank (`HipFbank`) on the GPU, so the features never exist on the host.  Everything from `input_features` on
@@ -160,6 +167,7 @@ class Wav2VecBert(HbmFeaturePlugin):
     name: tp.Literal["Wav2VecBert"] = "Wav2VecBert"
     pretrained: str = "facebook/w2v-bert-2.0"             # audio.py:47,222; resolved from the local HF cache only
     frontend: tp.Literal["hf", "hip"] = "hf"              # a route, not a result: kept out of the class uid like `device`
+    resampler: tp.Literal["scipy", "hip"] = "scipy"       # a result: julius' filter ("hip") is not scipy's, see `_item_uid`
     _EVENT_TYPE: tp.ClassVar[str] = "Sound"
     _KIND: tp.ClassVar[str] = "sampled"
     _model: tp.Any = pydantic.PrivateAttr(default=None)
@@ -211,7 +219,8 @@ class Wav2VecBert(HbmFeaturePlugin):
         return getattr(self.feature_extractor, "sampling_rate", 16_000)
 
     def _item_uid(self, event: tp.Any) -> str:
-        return f"{event.filepath}_{event.offset:.2f}_{event.duration:.2f}"
+        uid = f"{event.filepath}_{event.offset:.2f}_{event.duration:.2f}"
+        return uid + "_julius" if self.resampler == "hip" else uid     # the cache is keyed by item uid alone: keep the two filters apart
 
     def _preprocess_wav(self, wav: torch.Tensor) -> torch.Tensor:
         wav = torch.mean(wav, dim=1)                                   # audio.py:123-127: mono, z-scored
@@ -258,8 +267,13 @@ class Wav2VecBert(HbmFeaturePlugin):
                 wav, sfreq = torch.as_tensor(got, dtype=torch.float32), event.frequency
             if wav.ndim == 1:
                 wav = wav[:, None]
-            wav = self._resample_wav(wav, sfreq, self._input_frequency)
             timepoints = Frequency(2.0).to_ind(event.duration)
+            if self.resampler == "hip":                                 # one upload at the native rate; 16 kHz exists on the GPU only
+                wav = ops.resample_frac(wav.contiguous().to(self.model.device), int(sfreq), int(self._input_frequency))[0]
+                if self.frontend != "hip":
+                    wav = wav.cpu()                                     # the HF extractor works on the host
+            else:
+                wav = self._resample_wav(wav, sfreq, self._input_frequency)
             if self.frontend == "hip":
                 yield self._process_wav_hip(wav, timepoints).cpu().numpy()
             else:

@@ -275,6 +275,7 @@ SIGNATURES = {
     "tribe_rank_reduce": (C.c_int, [vp, i64, f32, vp, vp]),
     "tribe_fbank_workspace_bytes": (sz, [C.POINTER(i64), i32]),
     "tribe_fbank_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, vp, vp, vp, i64, C.POINTER(i32), vp, sz, vp]),
+    "tribe_resample_frac_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.POINTER(i64), vp]),
     "tribe_video_preprocess_workspace_bytes": (sz, [i64, i32, i32, i32]),
     "tribe_video_preprocess_fwd": (C.c_int, [vp, i64, i32, i32, vp, i64, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
 }

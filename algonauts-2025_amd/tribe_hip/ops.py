@@ -5,6 +5,8 @@ stream to libtribe_hip.so.  torch is used for memory, streams and nothing else."
 from __future__ import annotations
 
 import ctypes as C
+import functools as _functools
+import math as _math
 import typing as tp
 
 import numpy as _np
@@ -949,6 +951,99 @@ def w2vbert_fbank(wavs: torch.Tensor | tp.Sequence[torch.Tensor], zscore: bool =
                                 got, ws.data_ptr(), ws.numel(), _stream()), "tribe_fbank_fwd")
     assert list(got) == lengths
     return out, lengths
+
+
+# --------------------------------------------------------------------------------------
+# Wav2Vec-BERT audio front end: native-rate waveform -> 16 kHz, julius' windowed-sinc filter (csrc/resample.hip)
+# --------------------------------------------------------------------------------------
+RESAMPLE_MAX_CHUNKS = 32                      # TRIBE_RESAMPLE_MAX_CHUNKS
+RESAMPLE_TABLE_MAX_BYTES = 64 << 20           # the cap of tribe_resample_frac_fwd
+
+
+@_functools.lru_cache(maxsize=16)
+def julius_resample_kernels(old_sr: int, new_sr: int, zeros: int = 24, rolloff: float = 0.945) -> tuple[int, int, int, torch.Tensor]:
+    """The polyphase filter bank of `julius.resample.ResampleFrac(old_sr, new_sr, zeros, rolloff)` (julius 0.2.7, the reference's
+    audio.py:129-138): (old, new, width, table f32 [new, 2 * width + old]) with old / new the rates divided by their gcd.  Row i
+    filters output phase i: a sinc low-pass at min(old, new) * rolloff, cut at `zeros` zero crossings by a squared-cosine window,
+    normalised to sum 1.  It is built in FLOAT32 WITH THE TORCH OPS JULIUS USES, in its order, because the precision is part of what
+    the reference computes: a float64 table differs by up to 3.4e-5 per tap at 441 / 160.  julius is not installed here: this is a
+    restatement of its published source, and parity with the package itself is not executed.  Equal rates give an empty table of
+    width 0 (nothing to filter); a table above 64 MiB (44100 -> 16001 asks for gigabytes) is a ValueError."""
+    old_sr, new_sr = int(old_sr), int(new_sr)
+    if old_sr < 1 or new_sr < 1:
+        raise ValueError(f"julius_resample_kernels: rates must be >= 1, got {old_sr} -> {new_sr}")
+    g = _math.gcd(old_sr, new_sr)
+    old, new = old_sr // g, new_sr // g
+    if old == new:
+        return old, new, 0, torch.zeros(new, 0, dtype=torch.float32)
+    sr = min(new, old) * rolloff
+    width = _math.ceil(zeros * old / sr)
+    taps = 2 * width + old
+    if new * taps * 4 > RESAMPLE_TABLE_MAX_BYTES:
+        raise ValueError(f"julius_resample_kernels: {old_sr} -> {new_sr} reduces to {old} / {new}: a table of {new} x {taps} float32 "
+                         f"is above {RESAMPLE_TABLE_MAX_BYTES >> 20} MiB")
+    idx = torch.arange(-width, width + old).float()
+    rows = []
+    for i in range(new):
+        t = (-i / new + idx / old) * sr
+        t.clamp_(-zeros, zeros)
+        t *= _math.pi
+        window = torch.cos(t / zeros / 2) ** 2
+        kernel = torch.where(t == 0, torch.tensor(1.0, dtype=t.dtype), torch.sin(t) / t) * window
+        kernel.div_(kernel.sum())
+        rows.append(kernel)
+    return old, new, width, torch.stack(rows).contiguous()
+
+
+def resample_output_length(n: int, old_sr: int, new_sr: int) -> int:
+    """Samples julius returns for n input samples: `floor(float32(new * n / old))` -- the division is a Python double and
+    `torch.as_tensor` rounds it to float32 before the floor, so this is NOT `new * n // old` (441 / 160: n = 299993 gives 108841,
+    one more) -- and never more than the (n // old + 1) * new samples its strided convolution produces."""
+    n, g = int(n), _math.gcd(int(old_sr), int(new_sr))
+    old, new = int(old_sr) // g, int(new_sr) // g
+    if old == new or n <= 0:
+        return max(n, 0)
+    return min(int(_math.floor(float(_np.float32(new * n / old)))), (n // old + 1) * new)
+
+
+_RESAMPLE_TABLES: dict[tuple[int, int, int], torch.Tensor] = {}
+
+
+def resample_frac(wavs: torch.Tensor | tp.Sequence[torch.Tensor], old_sr: int, new_sr: int) -> list[torch.Tensor]:
+    """Waveform chunk(s) f32 [n] or [n, channels] (sample-major, on the GPU) at old_sr -> the same at new_sr, each channel through
+    julius' `ResampleFrac` filter (`julius_resample_kernels`), `resample_output_length(n)` samples per chunk.  One launch for all
+    chunks; a chunk's samples are the same bits alone or in a batch, and a channel's the same bits whatever the channel count.
+    Equal rates return the inputs themselves.  A chunk too short to yield a sample (n = 1 at 3 / 1) comes back empty."""
+    chunks = [wavs] if isinstance(wavs, torch.Tensor) else list(wavs)
+    if not 1 <= len(chunks) <= RESAMPLE_MAX_CHUNKS:
+        raise ValueError(f"resample_frac: {len(chunks)} chunks (1 to {RESAMPLE_MAX_CHUNKS} per call)")
+    for i, w in enumerate(chunks):
+        if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32 or not w.is_contiguous():
+            raise ValueError(f"resample_frac: wavs[{i}] must be a contiguous float32 tensor on the GPU (there is no host path)")
+        if w.ndim not in (1, 2) or w.device != chunks[0].device:
+            raise ValueError(f"resample_frac: wavs[{i}] must be [n] or [n, channels] on one device, got {tuple(w.shape)} on {w.device}")
+        if w.shape[0] < 1:
+            raise ValueError(f"resample_frac: wavs[{i}] is empty")
+    channels = {1 if w.ndim == 1 else int(w.shape[1]) for w in chunks}
+    if len(channels) != 1 or min(channels) < 1:
+        raise ValueError(f"resample_frac: chunks of one call share a channel count >= 1, got {sorted(channels)}")
+    old, new, width, table = julius_resample_kernels(int(old_sr), int(new_sr))
+    if old == new:
+        return chunks
+    device = chunks[0].device
+    key = (device.index if device.index is not None else torch.cuda.current_device(), old, new)
+    if key not in _RESAMPLE_TABLES:
+        _RESAMPLE_TABLES[key] = table.to(device)
+    n_out = [resample_output_length(int(w.shape[0]), old, new) for w in chunks]
+    outs = [torch.empty((m,) + tuple(w.shape[1:]), dtype=torch.float32, device=device) for w, m in zip(chunks, n_out)]
+    run = [i for i, m in enumerate(n_out) if m > 0]
+    if run:
+        B = len(run)
+        check(lib().tribe_resample_frac_fwd((C.c_void_p * B)(*[chunks[i].data_ptr() for i in run]), (C.c_int64 * B)(*[int(chunks[i].shape[0]) for i in run]),
+                                            B, channels.pop(), old, new, width, _RESAMPLE_TABLES[key].data_ptr(),
+                                            (C.c_void_p * B)(*[outs[i].data_ptr() for i in run]), (C.c_int64 * B)(*[n_out[i] for i in run]), _stream()),
+              "tribe_resample_frac_fwd")
+    return outs
 
 
 # --------------------------------------------------------------------------------------

@@ -601,6 +601,25 @@ int tribe_fbank_fwd(const float* const* wavs_host, const int64_t* n_host, int32_
                     const float* window, const float* mel, float* out, int64_t T_max, int32_t* lengths_host, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- audio front end: native-rate waveform -> 16 kHz (data_utils/features/audio.py:129-138 `julius.resample.ResampleFrac`) ----
+ * Replaces the resampler in front of the filterbank with julius' windowed-sinc polyphase filter.  old_sr / new_sr are the REDUCED
+ * rates (divided by their gcd; 44100 -> 16000 is 441 / 160), width = W of the filter, K = 2 * width + old_sr taps per phase;
+ * `table`: DEVICE f32 [new_sr, K], built on the host in float32 by `data_utils.features.audio.julius_resample_kernels`
+ * (zeros = 24, rolloff = 0.945).  For chunk b, channel c, frame f and phase i < new_sr, with j = f * new_sr + i < n_out_host[b]:
+ *   out[j, c] = sum_{k < K} table[i, k] * wav[clamp(f * old_sr + k - width, 0, n - 1), c]
+ * (julius' replicate padding), one f32 fma chain in k order.  wavs_host / out_host: B device pointers each in HOST arrays, chunk b
+ * f32 [n_host[b], channels] -> f32 [n_out_host[b], channels], both sample-major, so out_host can be tribe_fbank_fwd's wavs_host.
+ * n_out_host[b] is julius' output length (`resample_output_length`: floor of new_sr * n / old_sr rounded to float32, NOT the
+ * integer floor); nothing is written at or past it.  Checked before anything is launched (a violation returns < 0): B in 1 ..
+ * TRIBE_RESAMPLE_MAX_CHUNKS; channels >= 1; both rates >= 1, different and coprime; width >= 1; the table at most 64 MiB (44100 ->
+ * 16001 would ask for gigabytes); n >= 1; 1 <= n_out <= (n / old_sr + 1) * new_sr, the samples the strided convolution has; no
+ * null or misaligned pointer.  Asynchronous, one launch, no workspace, no allocation; a chunk's samples do not depend on the rest
+ * of the batch or on the channel count, bit for bit. */
+#define TRIBE_RESAMPLE_MAX_CHUNKS 32
+int tribe_resample_frac_fwd(const float* const* wavs_host, const int64_t* n_host, int32_t B, int32_t channels, int32_t old_sr,
+                            int32_t new_sr, int32_t width, const float* table, float* const* out_host, const int64_t* n_out_host,
+                            void* stream);
+
 /* ---- video front end: decoded uint8 frames -> V-JEPA2 pixel_values_videos (data_utils/features/video.py `default_video_processor`) ----
  * Replaces the host processor in front of the ViT: antialiased bilinear resize (torch's `interpolate(mode="bilinear",
  * antialias=True)`: a separable triangle filter) of frames to resized_h x resized_w, a crop window of crop x crop, / 255,
