@@ -629,6 +629,66 @@ __global__ __launch_bounds__(256) void segment_mean4_kernel(const float* __restr
   atomicAdd(o, acc[0].x * inv); atomicAdd(o + 1, acc[0].y * inv); atomicAdd(o + 2, acc[0].z * inv); atomicAdd(o + 3, acc[0].w * inv);
 }
 
+// means over a LIST of windows (several per sequence, overlapping or equal): one workgroup per (window, column block), V columns per lane
+// (V = 4: 16-byte loads and stores).  A lane sums the rows of its window first to last into one accumulator (U loads in flight, added in row
+// order), divides once and stores once: no atomics, no memset, the same bits on every launch.  Windows are word-sized, so a window is not split.
+// The window is clamped into [0, T] before anything is read; an empty window or a sequence index outside [0, B) stores zeros.
+template <int V>
+__global__ __launch_bounds__(256) void window_mean_kernel(const float* __restrict__ x, int64_t B, int64_t T, int64_t dim,
+                                                          const int64_t* __restrict__ win_row, const int64_t* __restrict__ win_start,
+                                                          const int64_t* __restrict__ win_len, int64_t col_blocks, float* __restrict__ out,
+                                                          int64_t ld_out) {
+  constexpr int U = 4;
+  const int64_t w = (int64_t)blockIdx.x / col_blocks;
+  const int64_t c = (((int64_t)blockIdx.x % col_blocks) * blockDim.x + threadIdx.x) * V;
+  if (c >= dim) return;
+  const int64_t b = win_row[w];
+  int64_t s = win_start[w], n = win_len[w];
+  if (s < 0) s = 0;
+  if (s > T) s = T;
+  if (n > T - s) n = T - s;   // never s + n: the sum of two unchecked device values may wrap
+  if (b < 0 || b >= B || n < 0) n = 0;
+  float acc[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) acc[v] = 0.f;
+  if (n > 0) {
+    const float* p = x + (b * T + s) * dim + c;
+    int64_t t = 0;
+    for (; t + U <= n; t += U) {
+      float r[U][V];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if constexpr (V == 4) {
+          const float4 q = *reinterpret_cast<const float4*>(p + (t + u) * dim);
+          r[u][0] = q.x; r[u][1] = q.y; r[u][2] = q.z; r[u][3] = q.w;
+        } else {
+          r[u][0] = p[(t + u) * dim];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[v] += r[u][v];
+    }
+    for (; t < n; ++t) {
+      if constexpr (V == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p + t * dim);
+        acc[0] += q.x; acc[1] += q.y; acc[2] += q.z; acc[3] += q.w;
+      } else {
+        acc[0] += p[t * dim];
+      }
+    }
+    const float fn = (float)n;
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc[v] = acc[v] / fn;
+  }
+  float* o = out + w * ld_out + c;
+  if constexpr (V == 4)
+    *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  else
+    o[0] = acc[0];
+}
+
 // ---------------------------------------------------------------------------------
 // row softmax: S f32 [R, T] (ld_s) -> P bf16 [R, T_pad] (ld_p), zero padded; one wave per row
 // ---------------------------------------------------------------------------------
@@ -939,6 +999,25 @@ extern "C" int tribe_segment_mean_fwd(const float* x, int64_t B, int64_t T, int6
   }
   dim3 grid((unsigned)((dim + 255) / 256), (unsigned)B, (unsigned)slices);
   hipLaunchKernelGGL(segment_mean_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, T, dim, start, len, out, ld_out);
+  TRIBE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tribe_window_mean_fwd(const float* x, int64_t B, int64_t T, int64_t dim, const int64_t* win_row, const int64_t* win_start,
+                                     const int64_t* win_len, int64_t W, float* out, int64_t ld_out, void* stream) {
+  TRIBE_REQUIRE(x && win_row && win_start && win_len && out, "tribe_window_mean_fwd: null pointer");
+  TRIBE_REQUIRE(B > 0 && T > 0 && dim > 0 && W > 0 && ld_out >= dim, "tribe_window_mean_fwd: bad shape");
+  const bool vec = dim % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0 && ld_out % 4 == 0;
+  const int64_t col_blocks = vec ? (dim / 4 + 255) / 256 : (dim + 255) / 256;
+  TRIBE_REQUIRE(W <= INT32_MAX / col_blocks, "tribe_window_mean_fwd: W=%lld windows x %lld column blocks exceed the grid", (long long)W,
+                (long long)col_blocks);
+  const dim3 grid((unsigned)(W * col_blocks));
+  if (vec)
+    hipLaunchKernelGGL(window_mean_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, B, T, dim, win_row, win_start, win_len, col_blocks, out,
+                       ld_out);
+  else
+    hipLaunchKernelGGL(window_mean_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, B, T, dim, win_row, win_start, win_len, col_blocks, out,
+                       ld_out);
   TRIBE_LAUNCH_CHECK();
   return 0;
 }

@@ -87,40 +87,43 @@ extern "C" size_t tribe_llama_workspace_bytes(const tribe_llama_desc* d) {
   return ws.off;
 }
 
-extern "C" int tribe_llama_fwd(const tribe_llama_desc* d, float* states, void* workspace, size_t workspace_bytes, void* stream) {
-  TRIBE_REQUIRE(d && states && workspace, "tribe_llama_fwd: null pointer");
+namespace {
+// The forward both Llama entry points run; they differ in `pool(src, state)` alone, which averages the f32 [B*T, dim] hidden state `src`
+// into slot `state` (0 = embeddings ... depth = after the final RMSNorm) of the caller's output.
+template <typename Pool>
+int llama_forward(const char* who, const tribe_llama_desc* d, void* workspace, size_t workspace_bytes, void* stream, Pool pool) {
   TRIBE_REQUIRE(d->B > 0 && d->T > 0 && d->dim > 0 && d->depth >= 0 && d->heads_q > 0 && d->heads_kv > 0 && d->inter > 0,
-                "tribe_llama_fwd: bad shape");
-  TRIBE_REQUIRE(d->heads_q % d->heads_kv == 0, "tribe_llama_fwd: heads_q=%d not a multiple of heads_kv=%d", d->heads_q, d->heads_kv);
+                "%s: bad shape", who);
+  TRIBE_REQUIRE(d->heads_q % d->heads_kv == 0, "%s: heads_q=%d not a multiple of heads_kv=%d", who, d->heads_q, d->heads_kv);
   TRIBE_REQUIRE(d->dim % 64 == 0 && d->inter % 64 == 0 && (d->heads_q * d->dim_head) % 64 == 0,
-                "tribe_llama_fwd: dim, inter and heads_q*dim_head must be multiples of 64");
+                "%s: dim, inter and heads_q*dim_head must be multiples of 64", who);
   TRIBE_REQUIRE(d->embed && d->ids && d->final_norm_w && d->cos_tab && d->sin_tab && (d->depth == 0 || d->layers_host),
-                "tribe_llama_fwd: missing parameter pointer");
-  TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "tribe_llama_fwd: workspace must be 256-byte aligned");
+                "%s: missing parameter pointer", who);
+  TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", who);
   Arena ws(workspace);
   const LlamaLayout p = layout(d, ws);
-  TRIBE_REQUIRE(workspace_bytes >= ws.off, "tribe_llama_fwd: workspace too small");
+  TRIBE_REQUIRE(workspace_bytes >= ws.off, "%s: workspace too small", who);
   float *x = p.x, *fin = p.fin;
   uint16_t *xn = p.xn, *qkv = p.qkv, *ao = p.ao, *act = p.act;
   uint8_t* q8 = p.q8;
-  const int64_t M = p.M, dim = d->dim, BD = d->B * dim;
+  const int64_t M = p.M, dim = d->dim;
   TRIBE_REQUIRE(!d->fp8_host || (d->dim % 128 == 0 && p.q_w % 128 == 0 && d->inter % 128 == 0),
-                "tribe_llama_fwd: the fp8 path needs dim, heads_q * dim_head and inter to be multiples of 128");
-  TRIBE_REQUIRE(!(d->fp8_host && d->amax_out), "tribe_llama_fwd: calibrate (amax_out) on the bf16 path, not together with fp8_host");
+                "%s: the fp8 path needs dim, heads_q * dim_head and inter to be multiples of 128", who);
+  TRIBE_REQUIRE(!(d->fp8_host && d->amax_out), "%s: calibrate (amax_out) on the bf16 path, not together with fp8_host", who);
   // Linear `which` (0 qkv, 1 o, 2 gate_up, 3 down) of layer l on the bf16 or the fp8 route
   auto linear = [&](int l, int which, tribe_gemm_desc g, bool a_is_q8 = false) {
-    return extractor_linear("tribe_llama_fwd", d->fp8_host, d->amax_out, l, which, g, q8, stream, a_is_q8);
+    return extractor_linear(who, d->fp8_host, d->amax_out, l, which, g, q8, stream, a_is_q8);
   };
 
   int rc = tribe_embedding_fwd(d->embed, d->embed_dtype, d->ids, M, dim, d->vocab, x, stream);
   if (rc) return rc;
-  rc = tribe_segment_mean_fwd(x, d->B, d->T, dim, d->pool_start, d->pool_len, states, dim, stream);
+  rc = pool(x, 0);
   if (rc) return rc;
 
   for (int l = 0; l < d->depth; ++l) {
     const tribe_llama_layer& L = d->layers_host[l];
     TRIBE_REQUIRE(L.input_norm_w && L.w_qkv && L.w_o && L.post_norm_w && L.w_gate_up && L.w_down,
-                  "tribe_llama_fwd: layer %d has a null parameter", l);
+                  "%s: layer %d has a null parameter", who, l);
     bool q_in = false;
     rc = extractor_norm(d->fp8_host, l, 0, x, M, dim, L.input_norm_w, nullptr, 0, d->rms_eps, xn, q8, stream, &q_in);
     if (rc) return rc;
@@ -148,7 +151,7 @@ extern "C" int tribe_llama_fwd(const tribe_llama_desc* d, float* states, void* w
     rc = linear(l, 3, Linear(TRIBE_ROLE_FF2, M, act, d->inter, L.w_down, nullptr, x, dim, TRIBE_F32).residual(x));
     if (rc) return rc;
     if (l + 1 < d->depth) {
-      rc = tribe_segment_mean_fwd(x, d->B, d->T, dim, d->pool_start, d->pool_len, states + (int64_t)(l + 1) * BD, dim, stream);
+      rc = pool(x, l + 1);
       if (rc) return rc;
     }
   }
@@ -156,9 +159,29 @@ extern "C" int tribe_llama_fwd(const tribe_llama_desc* d, float* states, void* w
   if (d->depth > 0) {
     rc = tribe_rmsnorm_fwd(x, M, dim, d->final_norm_w, d->rms_eps, fin, TRIBE_F32, stream);
     if (rc) return rc;
-    rc = tribe_segment_mean_fwd(fin, d->B, d->T, dim, d->pool_start, d->pool_len, states + (int64_t)d->depth * BD, dim, stream);
+    rc = pool(fin, d->depth);
   }
   return rc;
+}
+}  // namespace
+
+extern "C" int tribe_llama_fwd(const tribe_llama_desc* d, float* states, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(d && states && workspace, "tribe_llama_fwd: null pointer");
+  return llama_forward("tribe_llama_fwd", d, workspace, workspace_bytes, stream, [&](const float* src, int state) {
+    return tribe_segment_mean_fwd(src, d->B, d->T, d->dim, d->pool_start, d->pool_len, states + (int64_t)state * d->B * d->dim, d->dim, stream);
+  });
+}
+
+// the same workspace: the window list changes what is pooled, not what is computed
+extern "C" size_t tribe_llama_windows_workspace_bytes(const tribe_llama_desc* d) { return tribe_llama_workspace_bytes(d); }
+
+extern "C" int tribe_llama_windows_fwd(const tribe_llama_desc* d, const int64_t* win_row, const int64_t* win_start, const int64_t* win_len,
+                                       int64_t W, float* states, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(d && win_row && win_start && win_len && states && workspace, "tribe_llama_windows_fwd: null pointer");
+  TRIBE_REQUIRE(W > 0, "tribe_llama_windows_fwd: W=%lld windows", (long long)W);
+  return llama_forward("tribe_llama_windows_fwd", d, workspace, workspace_bytes, stream, [&](const float* src, int state) {
+    return tribe_window_mean_fwd(src, d->B, d->T, d->dim, win_row, win_start, win_len, W, states + (int64_t)state * W * d->dim, d->dim, stream);
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -72,16 +72,19 @@ class ExtractorHost:
         self.fp8_layers = layers
         return table
 
-    def _launch(self, d: C.Structure, states: torch.Tensor, fp8: bool | None, amax: torch.Tensor | None, caller: str) -> torch.Tensor:
+    def _launch(self, d: C.Structure, states: torch.Tensor, fp8: bool | None, amax: torch.Tensor | None, caller: str,
+                forward: str | None = None, extra: tuple[tp.Any, ...] = ()) -> torch.Tensor:
         """The tail of every forward: d is the filled descriptor but for fp8_host / amax_out; fp8 None = the e4m3 GEMMs when enable_fp8()
-        has run; amax = the calibration table to fill (a bf16 pass).  Returns `states`, written by FORWARD on the current stream."""
+        has run; amax = the calibration table to fill (a bf16 pass).  Returns `states`, written by FORWARD on the current stream.
+        `forward` names another entry point that takes the same descriptor, with `extra` arguments between it and `states`."""
+        forward = forward or self.FORWARD
         if (self.fp8_layers is not None if fp8 is None else fp8) and amax is None:
             if self.fp8_layers is None:
                 raise ValueError(f"{caller}(fp8=True) before enable_fp8()")
             d.fp8_host = C.cast(self.fp8_layers, C.POINTER(self.FP8_LAYER))
         if amax is not None:
             d.amax_out = amax.data_ptr()
-        nbytes = getattr(lib(), self.FORWARD.replace("_fwd", "_workspace_bytes"))(C.byref(d))
+        nbytes = getattr(lib(), forward.replace("_fwd", "_workspace_bytes"))(C.byref(d))
         ws = ops.workspace(nbytes, self.device, "extractor")
-        check(getattr(lib(), self.FORWARD)(C.byref(d), states.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), self.FORWARD)
+        check(getattr(lib(), forward)(C.byref(d), *extra, states.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()), forward)
         return states

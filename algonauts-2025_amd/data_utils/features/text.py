@@ -10,6 +10,10 @@ Here the model forward AND the pooling run in one C call (`tribe_llama_fwd`: RMS
 causal grouped-query flash attention, SwiGLU GEMM epilogue, f32 residual stream); only `[B, n_states, hidden]` floats
 leave the GPU, where the reference copies every hidden state to the host (text.py:240).
 
+`LLAMA3p2(share_prefixes=True)` runs one forward per RUN of nested contexts instead of one per word (`prefix_groups`,
+`HipLlamaModel.forward_windows` -> `tribe_llama_windows_fwd`): exact while each context is a prefix of the next, which ends
+where the cap on the context length starts to drop words on the left.  Off by default.
+
 Weights come from any `transformers` LlamaModel / state_dict (names `embed_tokens.weight`,
 `layers.N.self_attn.{q,k,v,o}_proj.weight`, `layers.N.mlp.{gate,up,down}_proj.weight`, `layers.N.*layernorm.weight`,
 `norm.weight`).  The reference fetches `meta-llama/Llama-3.2-3B` by name; that checkpoint is not available offline, so
@@ -116,17 +120,13 @@ class HipLlamaModel(ExtractorHost):
         zeros, full = torch.zeros(B, dtype=torch.int64), torch.full((B,), T, dtype=torch.int64)
         self.forward_pooled(calibration_ids, zeros, full, _amax=amax)
 
-    def forward_pooled(self, input_ids: torch.Tensor, pool_start: torch.Tensor, pool_len: torch.Tensor, fp8: bool | None = None,
-                       _amax: torch.Tensor | None = None) -> torch.Tensor:
-        """input_ids int64 [B, T] (right padded); returns f32 [n_layers + 1, B, dim]: every hidden state averaged over
-        positions [pool_start[b], pool_start[b] + pool_len[b]).  fp8: None = use the e4m3 GEMMs when enable_fp8() has run."""
+    def _describe(self, input_ids: torch.Tensor) -> tuple[LlamaDesc, torch.Tensor]:
+        """The descriptor of one forward over input_ids [B, T], but for what is pooled, and the device ids it points to."""
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         B, T = ids.shape
         if int(ids.min()) < 0 or int(ids.max()) >= self.vocab:
             raise ValueError("token id outside the vocabulary")
         cos, sin = self._tables(T)
-        start = pool_start.to(device=self.device, dtype=torch.int64).contiguous()
-        length = pool_len.to(device=self.device, dtype=torch.int64).contiguous()
         d = LlamaDesc()
         d.B, d.T = B, T
         d.dim, d.depth, d.heads_q, d.heads_kv, d.dim_head, d.inter = self.dim, self.depth, self.heads_q, self.heads_kv, self.dim_head, self.inter
@@ -135,9 +135,63 @@ class HipLlamaModel(ExtractorHost):
         d.layers_host = C.cast(self.layers, C.POINTER(LlamaLayer))
         d.final_norm_w = self.final_norm.data_ptr()
         d.cos_tab, d.sin_tab = cos.data_ptr(), sin.data_ptr()
-        d.ids, d.pool_start, d.pool_len = ids.data_ptr(), start.data_ptr(), length.data_ptr()
-        states = torch.empty(self.depth + 1, B, self.dim, dtype=torch.float32, device=self.device)
+        d.ids = ids.data_ptr()
+        return d, ids
+
+    def forward_pooled(self, input_ids: torch.Tensor, pool_start: torch.Tensor, pool_len: torch.Tensor, fp8: bool | None = None,
+                       _amax: torch.Tensor | None = None) -> torch.Tensor:
+        """input_ids int64 [B, T] (right padded); returns f32 [n_layers + 1, B, dim]: every hidden state averaged over
+        positions [pool_start[b], pool_start[b] + pool_len[b]).  fp8: None = use the e4m3 GEMMs when enable_fp8() has run."""
+        d, ids = self._describe(input_ids)
+        start = pool_start.to(device=self.device, dtype=torch.int64).contiguous()
+        length = pool_len.to(device=self.device, dtype=torch.int64).contiguous()
+        d.pool_start, d.pool_len = start.data_ptr(), length.data_ptr()
+        states = torch.empty(self.depth + 1, ids.shape[0], self.dim, dtype=torch.float32, device=self.device)
         return self._launch(d, states, fp8, _amax, "forward_pooled")
+
+    def forward_windows(self, input_ids: torch.Tensor, win_row: tp.Any, win_start: tp.Any, win_len: tp.Any,
+                        fp8: bool | None = None) -> torch.Tensor:
+        """The same forward pooled over a LIST of W windows: window w averages positions [win_start[w], win_start[w] + win_len[w]) of
+        row win_row[w]; several windows may share a row, overlap or repeat.  Returns f32 [n_layers + 1, W, dim].  With the causal mask
+        and right padding, position t sees tokens 0..t only, so one row holding the longest of a run of nested contexts gives the
+        states of every shorter one (see prefix_groups).  Windows are validated here, on the host, before anything is launched."""
+        row, start, length = (torch.as_tensor(t, dtype=torch.int64).cpu().flatten() for t in (win_row, win_start, win_len))
+        B, T = input_ids.shape
+        W = row.numel()
+        if W == 0 or start.numel() != W or length.numel() != W:
+            raise ValueError(f"forward_windows: win_row, win_start and win_len must have one length > 0, got {W} / {start.numel()} / {length.numel()}")
+        if int(row.min()) < 0 or int(row.max()) >= B:
+            raise ValueError(f"forward_windows: win_row outside [0, {B})")
+        if int(start.min()) < 0 or int(length.min()) < 0 or int((start + length).max()) > T:
+            raise ValueError(f"forward_windows: a window leaves [0, {T})")
+        d, ids = self._describe(input_ids)
+        wins = torch.stack([row, start, length]).to(self.device)   # one upload: rows 0 / 1 / 2 of an int64 [3, W]
+        states = torch.empty(self.depth + 1, W, self.dim, dtype=torch.float32, device=self.device)
+        extra = (wins[0].data_ptr(), wins[1].data_ptr(), wins[2].data_ptr(), W)
+        return self._launch(d, states, fp8, None, "forward_windows", forward="tribe_llama_windows_fwd", extra=extra)
+
+
+def prefix_groups(token_rows: tp.Sequence[tp.Sequence[int]]) -> list[tuple[list[int], list[int]]]:
+    """Runs of nested contexts.  Walks the real (unpadded) token rows in the order given and returns, per group, (the group's longest
+    row, the indices of its members).  A row joins the current group when the group's longest row is a prefix of it (it becomes the
+    longest: the next word of a timeline) or when it is itself a prefix of the longest row (a repeat, a shorter context, an empty
+    one); any other row opens a new group.  The test is on token ids, not on strings: a tokenizer need not map a string prefix to a
+    token prefix.  Members of a group are consecutive inputs, and every member's tokens sit at the same positions in the longest row
+    as in its own, so `word_pool_windows` of the member addresses the longest row unchanged."""
+    groups: list[tuple[list[int], list[int]]] = []
+    for i, r in enumerate(token_rows):
+        row = [int(t) for t in r]
+        if groups:
+            longest, members = groups[-1]
+            n = len(longest)
+            if len(row) >= n and row[:n] == longest:
+                groups[-1] = (row, members + [i])
+                continue
+            if len(row) < n and longest[:len(row)] == row:
+                members.append(i)
+                continue
+        groups.append((row, [i]))
+    return groups
 
 
 def word_pool_windows(input_ids: torch.Tensor, target_words: tp.Sequence[str], pad_id: int) -> tuple[torch.Tensor, torch.Tensor]:
@@ -160,10 +214,20 @@ class LLAMA3p2(HbmFeaturePlugin):
     name: tp.Literal["LLAMA3p2"] = "LLAMA3p2"
     batch_size: int = 8                                   # text.py:212 (DataLoader batch of contexts)
     pretrained: str = "meta-llama/Llama-3.2-3B"           # text.py:166-173; resolved from the local HF cache only
+    share_prefixes: bool = False                          # one forward per run of nested contexts (a schedule, not a result): see extract
     _EVENT_TYPE: tp.ClassVar[str] = "Word"
     _KIND: tp.ClassVar[str] = "words"
     _model: tp.Any = pydantic.PrivateAttr(default=None)
     _tokenizer: tp.Any = pydantic.PrivateAttr(default=None)
+
+    @classmethod
+    def _exclude_from_cls_uid(cls) -> list[str]:
+        return super()._exclude_from_cls_uid() + ["share_prefixes"]
+
+    def _exclude_from_cache_uid(self) -> list[str]:
+        # a field at its default never enters a uid, so the schedule needs excluding only where it is set: a default plugin keeps the
+        # reference's list (text.py:157-158) as it is
+        return super()._exclude_from_cache_uid() + (["share_prefixes"] if self.share_prefixes else [])
 
     def attach(self, model: HipLlamaModel, tokenizer: tp.Any) -> "LLAMA3p2":
         """Provide weights + tokenizer explicitly (offline use: the reference fetches them by name)."""
@@ -194,7 +258,16 @@ class LLAMA3p2(HbmFeaturePlugin):
         return self.extract([e.text for e in events], [e.context for e in events])
 
     def extract(self, target_words: tp.Sequence[str], contexts: tp.Sequence[str]) -> tp.Iterator[np.ndarray]:
-        """The body of the reference's `_get_data` loop (text.py:204-256): yields [n_states, hidden] per word."""
+        """The body of the reference's `_get_data` loop (text.py:204-256): yields [n_states, hidden] per word.
+
+        share_prefixes: inside a timeline the context of word i + 1 is the context of word i plus one word, until the cap on the
+        context length starts to drop words on the left.  Such a run of N nested contexts takes ONE row -- its longest context --
+        and N pooling windows (`prefix_groups`, `forward_windows`) instead of N rows: ceil(groups / batch_size) forwards instead of
+        ceil(N / batch_size).  Once the context window slides, no context is a prefix of the next and every word is its own group:
+        those words still cost one forward each."""
+        if self.share_prefixes:
+            yield from self._extract_shared(target_words, contexts)
+            return
         model, tok = self.model, self.tokenizer
         pad_id = tok.eos_token_id
         for i in range(0, len(contexts), self.batch_size):
@@ -204,6 +277,30 @@ class LLAMA3p2(HbmFeaturePlugin):
             states = model.forward_pooled(enc["input_ids"], start, length).cpu().numpy()  # [n_states, B, dim]
             for j in range(len(words)):
                 yield states[:, j]
+
+    def _extract_shared(self, target_words: tp.Sequence[str], contexts: tp.Sequence[str]) -> tp.Iterator[np.ndarray]:
+        model, tok = self.model, self.tokenizer
+        pad_id = tok.eos_token_id
+        rows: list[list[int]] = []
+        windows: list[tuple[int, int]] = []
+        for i in range(0, len(contexts), self.batch_size):   # tokenised exactly as on the per-word route, then the padding is stripped
+            words, ctx = list(target_words[i:i + self.batch_size]), list(contexts[i:i + self.batch_size])
+            ids = tok(ctx, add_special_tokens=False, return_tensors="pt", padding=True, truncation=True)["input_ids"]
+            start, length = word_pool_windows(ids, words, pad_id)
+            for j in range(len(words)):
+                rows.append(ids[j, :int(start[j] + length[j])].tolist())   # start + length = the number of real tokens
+                windows.append((int(start[j]), int(length[j])))
+        groups = prefix_groups(rows)
+        for i in range(0, len(groups), self.batch_size):
+            batch = groups[i:i + self.batch_size]
+            ids = torch.full((len(batch), max(1, max(len(longest) for longest, _ in batch))), pad_id, dtype=torch.int64)
+            for g, (longest, _) in enumerate(batch):
+                ids[g, :len(longest)] = torch.tensor(longest, dtype=torch.int64)
+            win_row = [g for g, (_, members) in enumerate(batch) for _ in members]
+            win = [windows[m] for _, members in batch for m in members]
+            states = model.forward_windows(ids, win_row, [s for s, _ in win], [n for _, n in win]).cpu().numpy()  # [n_states, W, dim]
+            for w in range(len(win)):   # members of a group are consecutive inputs: this is the input order
+                yield states[:, w]
 
     def aggregate(self, latents: np.ndarray) -> np.ndarray:
         return self._aggregate_layers(latents)

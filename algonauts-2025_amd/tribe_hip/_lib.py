@@ -210,6 +210,7 @@ SIGNATURES = {
     "tribe_rmsnorm_fwd": (C.c_int, [vp, i64, i64, vp, f32, vp, i32, vp]),
     "tribe_layernorm_fwd": (C.c_int, [vp, i64, i64, vp, vp, f32, vp, i32, vp]),
     "tribe_segment_mean_fwd": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, i64, vp]),
+    "tribe_window_mean_fwd": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, i64, vp, i64, vp]),
     "tribe_im2col3d_fwd": (C.c_int, [vp, i64, i32, i32, i32, i32, i32, i32, vp, i64, vp]),
     "tribe_vjepa2_workspace_bytes": (sz, [C.POINTER(Vjepa2Desc)]),
     "tribe_vjepa2_fwd": (C.c_int, [C.POINTER(Vjepa2Desc), vp, vp, sz, vp]),
@@ -253,6 +254,8 @@ SIGNATURES = {
     "tribe_corr_matrix_fwd": (C.c_int, [vp, i64, i64, vp, vp, sz, vp]),
     "tribe_llama_workspace_bytes": (sz, [C.POINTER(LlamaDesc)]),
     "tribe_llama_fwd": (C.c_int, [C.POINTER(LlamaDesc), vp, vp, sz, vp]),
+    "tribe_llama_windows_workspace_bytes": (sz, [C.POINTER(LlamaDesc)]),
+    "tribe_llama_windows_fwd": (C.c_int, [C.POINTER(LlamaDesc), vp, vp, vp, i64, vp, vp, sz, vp]),
     "tribe_attention_workspace_bytes": (sz, [i64, i64, i32, i32]),
     "tribe_attention_lse_supported": (C.c_int, [i32, i32]),
     "tribe_attention_set_mode": (C.c_int, [i32]),

@@ -376,6 +376,22 @@ def segment_mean(x: torch.Tensor, B: int, T: int, start: torch.Tensor | None, le
     return out
 
 
+def window_mean(x: torch.Tensor, B: int, T: int, win_row: torch.Tensor, win_start: torch.Tensor, win_len: torch.Tensor) -> torch.Tensor:
+    """Means over a list of windows of x f32 [B*T, dim]: out[w] = mean of rows [win_start[w], win_start[w] + win_len[w]) of sequence win_row[w]
+    (int64 [W] each; windows may share a sequence, overlap or repeat) -> f32 [W, dim].  Clamped into [0, T]; an empty window or a sequence
+    outside [0, B) gives zeros.  Deterministic: the same bits on every launch."""
+    _cuda(x, torch.float32, "x")
+    row, start, length = (_cuda(t, torch.int64, name) for t, name in ((win_row, "win_row"), (win_start, "win_start"), (win_len, "win_len")))
+    dim, W = x.shape[-1], row.numel()
+    if x.numel() != B * T * dim or start.numel() != W or length.numel() != W:
+        raise ValueError(f"window_mean: x must hold {B * T} rows and the three window arrays one length, got {tuple(x.shape)} and "
+                         f"{W} / {start.numel()} / {length.numel()}")
+    out = torch.empty(W, dim, dtype=torch.float32, device=x.device)
+    check(lib().tribe_window_mean_fwd(x.data_ptr(), B, T, dim, row.data_ptr(), start.data_ptr(), length.data_ptr(), W, out.data_ptr(), dim,
+                                      _stream()), "tribe_window_mean_fwd")
+    return out
+
+
 def attention_set_mode(mode: int) -> None:
     """0 = fused kernels, picked per head size and grid (default); 1 = materialised-scores path (cross-check); 2 = the 16-row-per-wave
     kernel at every head size; 3 = dim_head 384 on the key-split kernel; 4 / 5 = dim_head 64 on the 4-wave / the anti-phase 8-wave kernel."""

@@ -287,6 +287,13 @@ int tribe_layernorm_fwd(const float* x, int64_t rows, int64_t dim, const float* 
  * non-pad positions; video.py:228: mean over all tokens).  x f32 [B*T, dim] -> out f32, row stride ld_out. */
 int tribe_segment_mean_fwd(const float* x, int64_t B, int64_t T, int64_t dim, const int64_t* start, const int64_t* len,
                            float* out, int64_t ld_out, void* stream);
+/* out[w, :] = mean_{t in [win_start[w], win_start[w]+win_len[w])} x[win_row[w]*T + t, :] for a LIST of W windows: several may name
+ * the same sequence, overlap or be equal (the words of nested contexts pooled from one forward).  x f32 [B*T, dim] -> out f32
+ * [W, dim], row stride ld_out; win_* are device int64 [W].  A window is clamped into [0, T] (start < 0 -> 0, the end cut to T); one
+ * that is empty after clamping, or whose win_row is outside [0, B), gives zeros and reads nothing.  Rows are summed first to last by
+ * one lane, divided once and stored once: no atomics and no memset, so two launches on the same input give the same bits. */
+int tribe_window_mean_fwd(const float* x, int64_t B, int64_t T, int64_t dim, const int64_t* win_row, const int64_t* win_start,
+                          const int64_t* win_len, int64_t W, float* out, int64_t ld_out, void* stream);
 
 /* Conv3d patch embedding with stride == kernel (VJEPA2PatchEmbeddings3D, modeling_vjepa2.py:84-117) as im2col:
  * pixels f32 [B, frames, chans, H, W] -> bf16 [B * tokens, K_pad], K = chans*tubelet*patch*patch in Conv3d weight order */
@@ -419,6 +426,15 @@ size_t tribe_llama_workspace_bytes(const tribe_llama_desc* d);
 /* LlamaModel forward with output_hidden_states (text.py:236-240) fused with the per-word pooling of
  * text.py:245-254: states f32 [depth + 1, B, dim] (state 0 = embeddings, last = after the final RMSNorm). */
 int tribe_llama_fwd(const tribe_llama_desc* d, float* states, void* workspace, size_t workspace_bytes, void* stream);
+
+size_t tribe_llama_windows_workspace_bytes(const tribe_llama_desc* d);
+/* The same forward (embedding, layers, final RMSNorm, bf16 or fp8 route, amax_out calibration) pooled over a LIST of W windows
+ * instead of one window per row: window w is positions [win_start[w], win_start[w] + win_len[w]) of row win_row[w] (device int64
+ * [W], semantics of tribe_window_mean_fwd); states f32 [depth + 1, W, dim].  d->pool_start and d->pool_len are ignored and may be
+ * NULL.  With a causal mask and right padding the state at position t depends on tokens 0..t only, so ONE row holding the longest
+ * of a run of nested contexts (each a prefix of the next) serves every word of the run -- as long as the contexts nest. */
+int tribe_llama_windows_fwd(const tribe_llama_desc* d, const int64_t* win_row, const int64_t* win_start, const int64_t* win_len,
+                            int64_t W, float* states, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * a7 + a8: SubjectLayers.forward (common.py:45-67) and AdaptiveAvgPool1d (model.py:119-120)
