@@ -577,8 +577,10 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restri
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= dim) return;
   int64_t s = start ? start[b] : 0, n = len ? len[b] : T;
-  if (s < 0) s = 0;
-  if (s + n > T) n = T - s;
+  if (n <= 0) return;             // also keeps n += s below from wrapping: n > 0 and s < 0 have opposite signs
+  if (s < 0) { n += s; s = 0; }   // the window is intersected with [0, T), as window_mean does: a negative start cuts it, it does not slide
+  if (s > T) s = T;
+  if (n > T - s) n = T - s;       // never s + n with s >= 0: the sum of two unchecked positive device values may wrap
   if (n <= 0) return;
   const int64_t per = (n + gridDim.z - 1) / gridDim.z;
   const int64_t t0 = (int64_t)blockIdx.z * per;
@@ -599,8 +601,10 @@ __global__ __launch_bounds__(256) void segment_mean4_kernel(const float* __restr
   const int64_t c = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (c >= dim) return;
   int64_t s = start ? start[b] : 0, n = len ? len[b] : T;
-  if (s < 0) s = 0;
-  if (s + n > T) n = T - s;
+  if (n <= 0) return;             // also keeps n += s below from wrapping: n > 0 and s < 0 have opposite signs
+  if (s < 0) { n += s; s = 0; }   // the window is intersected with [0, T), as window_mean does: a negative start cuts it, it does not slide
+  if (s > T) s = T;
+  if (n > T - s) n = T - s;       // never s + n with s >= 0: the sum of two unchecked positive device values may wrap
   if (n <= 0) return;
   const int64_t per = (n + gridDim.z - 1) / gridDim.z;
   const int64_t t0 = (int64_t)blockIdx.z * per;

@@ -17,6 +17,11 @@ Contents
                    bounds the GPU tests hold the kernels to, and f32 emulations
                    of the kernels' roundings with injectable faults.
 
+* `layout_ref`  -- float64 (and ordered-f32) references of the layout, gather and
+                   packing kernels between the GEMMs: im2col, the three rotary
+                   modes, the conv module, pools, window means, piece and CSR
+                   sums, and a bf16 rounding helper on bit patterns.
+
 Pinning status (see DESIGN.md "Oracle")
 ---------------------------------------
 * Everything that lives in the reference's own files (SubjectLayers,
