@@ -4,9 +4,10 @@ import typing as tp
 import pydantic
 
 from .base import (BaseMetricConfig, GroupedMetric, GroupedMetricConfig, MultidimPearsonCorrCoef,  # noqa: F401
-                   MultidimPearsonCorrCoefConfig, OnlinePearsonCorr)
+                   MultidimPearsonCorrCoefConfig, OnlinePearsonCorr, TorchMetricConfig)
 from .metrics import OnlinePearsonCorrConfig, Rank, RankConfig, TopkAcc, TopkAccConfig  # noqa: F401
+from .regression import ExplainedVariance, MeanAbsoluteError, MeanSquaredError, R2Score  # noqa: F401
 
 MetricConfig = tp.Annotated[tp.Union[MultidimPearsonCorrCoefConfig, GroupedMetricConfig, OnlinePearsonCorrConfig, RankConfig,
-                                     TopkAccConfig],
+                                     TopkAccConfig, TorchMetricConfig],
                             pydantic.Field(discriminator="name")]

@@ -12,10 +12,14 @@ f64 sufficient statistics {Sx, Sy, Sxx, Syy, Sxy, n} per (group, voxel) on the G
 which is what the reference's own evaluation uses (main.py:459-477).  The pandas groupby of
 base.py:67-78 is replaced by passing the group index of every batch row to the kernel.
 `sync()` all-reduces the statistics over the process group (RCCL) for multi-GPU evaluation.
+
+`TorchMetricConfig` / `GroupedMetric` also take the regression metrics of metrics/regression.py (MeanSquaredError,
+MeanAbsoluteError, R2Score, ExplainedVariance), which keep a [G, V, 6] state of their own.
 """
 
 from __future__ import annotations
 
+import inspect
 import typing as tp
 
 import pydantic
@@ -23,6 +27,8 @@ import torch
 from torch import nn
 
 from tribe_hip import ops
+
+from .regression import REGRESSION_METRICS
 
 
 class _PearsonState(nn.Module):
@@ -110,10 +116,12 @@ _BASE_METRICS = {"MultidimPearsonCorrCoef": MultidimPearsonCorrCoef, "OnlinePear
 class GroupedMetric(nn.Module):
     def __init__(self, metric_name: str, kwargs: dict[str, tp.Any] | None = None) -> None:
         super().__init__()
-        assert metric_name in _BASE_METRICS, f"Metric {metric_name} not found"
-        self.base_metric_cls = _BASE_METRICS[metric_name]
+        assert metric_name in _BASE_METRICS or metric_name in REGRESSION_METRICS, f"Metric {metric_name} not found"
+        self.base_metric_cls = _BASE_METRICS.get(metric_name) or REGRESSION_METRICS[metric_name]
         self.metric_kwargs = kwargs or {}
-        self._state: _PearsonState | None = None
+        # Pearson: one [G, V, 6] state made on the first update; regression: the sub-metric itself holds the [G, V, 6] state
+        self._regression = metric_name in REGRESSION_METRICS
+        self._state: tp.Any = self.base_metric_cls(**self.metric_kwargs) if self._regression else None
         self._ids: list[str] = []  # group keys in first-seen order (groupby(sort=False), base.py:67)
         self._index: dict[str, int] = {}
 
@@ -133,13 +141,22 @@ class GroupedMetric(nn.Module):
         slot = torch.tensor([self._index[str(lab)] for lab in labels], dtype=torch.int64, device=preds.device)
         if self._state is None:
             self._state = _PearsonState(preds.shape[1])
+        if preds.ndim == 1 and self._regression:  # [N]: one output
+            preds, target = preds.unsqueeze(-1), target.unsqueeze(-1)
         if preds.ndim == 2:  # [N, V]: every row is its own "batch row" of length T = 1
             preds, target = preds.float().unsqueeze(-1), target.float().unsqueeze(-1)
         self._state.update_bvt(preds, target, slot, len(self._ids))
 
     def compute(self) -> dict[str, float]:
-        if self._state is None:
+        if self._state is None or not self._ids:
             return {}
+        if self._regression:
+            scores = self._state.scores()  # [G], or [G, V] for a sub-metric that reports every output
+            if scores.ndim != 1:
+                raise ValueError(f"GroupedMetric needs one value per group, {self.base_metric_cls.__name__}({self.metric_kwargs}) gives "
+                                 f"{scores.shape[1]} (multioutput='raw_values' or num_outputs > 1)")
+            values = scores.tolist()
+            return {gid: values[self._index[gid]] for gid in self._ids}
         r = self._state.per_output()  # [G, V]
         means = r.mean(dim=1).tolist()
         return {gid: means[self._index[gid]] for gid in self._ids}
@@ -173,6 +190,23 @@ class MultidimPearsonCorrCoefConfig(BaseMetricConfig):
 
     def build(self) -> nn.Module:
         return MultidimPearsonCorrCoef(**self.kwargs)
+
+
+class TorchMetricConfig(BaseMetricConfig):
+    """The reference's TorchMetricConfig (base.py:116-127) for the torchmetrics regression metrics restated in metrics/regression.py;
+    `kwargs` are checked against the constructor of the class (its validate_kwargs)."""
+
+    name: tp.Literal["MeanSquaredError", "MeanAbsoluteError", "R2Score", "ExplainedVariance"]
+    kwargs: dict[str, tp.Any] = {}
+
+    def model_post_init(self, __context: tp.Any) -> None:
+        accepted = set(inspect.signature(REGRESSION_METRICS[self.name].__init__).parameters) - {"self"}
+        unknown = sorted(set(self.kwargs) - accepted)
+        if unknown:   # pydantic reports a ValueError raised here as a ValidationError
+            raise ValueError(f"{self.name}: unknown kwargs {unknown}; accepted: {sorted(accepted)}")
+
+    def build(self) -> nn.Module:
+        return REGRESSION_METRICS[self.name](**self.kwargs)
 
 
 class GroupedMetricConfig(BaseMetricConfig):

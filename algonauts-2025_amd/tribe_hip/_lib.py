@@ -276,6 +276,9 @@ SIGNATURES = {
     "tribe_retrieval_ranks": (C.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, vp, i32, vp, vp]),
     "tribe_retrieval_scores": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, vp, i32, vp, vp]),
     "tribe_rank_reduce": (C.c_int, [vp, i64, f32, vp, vp]),
+    "tribe_regression_stats_update": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i64, vp, i64, vp, vp]),
+    "tribe_regression_from_stats": (C.c_int, [vp, i64, i64, i32, vp, vp]),
+    "tribe_regression_reduce": (C.c_int, [vp, i64, i64, i32, i32, vp, vp]),
     "tribe_fbank_workspace_bytes": (sz, [C.POINTER(i64), i32]),
     "tribe_fbank_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, vp, vp, vp, i64, C.POINTER(i32), vp, sz, vp]),
     "tribe_resample_frac_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.POINTER(i64), vp]),

@@ -600,6 +600,63 @@ def pearson_loss(pred: torch.Tensor, true: torch.Tensor, reduction: str = "mean"
 
 
 # --------------------------------------------------------------------------------------
+# regression metrics MSE / RMSE / MAE / R2 / explained variance (csrc/regression_metrics.hip)
+# --------------------------------------------------------------------------------------
+REGRESSION_KINDS = {"mse": 0, "rmse": 1, "mae": 2, "r2": 3, "explained_variance": 4}     # enum tribe_regression_kind
+REGRESSION_MODES = {"pooled": 0, "uniform_average": 1, "variance_weighted": 2}           # enum tribe_regression_mode
+
+
+def regression_stats_update(stats: torch.Tensor, pred: torch.Tensor, true: torch.Tensor, group: torch.Tensor | None = None) -> None:
+    """stats f64 [G, V, 6] += {sum d, sum d^2, sum |d|, sum t, sum t^2, n} of d = true - pred over [B, V, T] views (any common
+    strides); group int64 [B] or None."""
+    _cuda(stats, torch.float64, "stats")
+    _cuda(pred, torch.float32, "pred", contiguous=False)
+    _cuda(true, torch.float32, "true", contiguous=False)
+    B, V, T, sb, sv, st = _bvt_strides(pred, true, "regression_stats_update")
+    G = stats.shape[0]
+    if stats.shape != (G, V, 6):
+        raise ValueError(f"regression_stats_update: stats must be [G, {V}, 6], got {tuple(stats.shape)}")
+    if group is not None:
+        _cuda(group, torch.int64, "group")
+        if group.numel() != B:
+            raise ValueError("regression_stats_update: group must have B entries")
+    check(lib().tribe_regression_stats_update(pred.data_ptr(), true.data_ptr(), B, V, T, sb, sv, st, _p(group), G, stats.data_ptr(),
+                                              _stream()), "tribe_regression_stats_update")
+
+
+def _regression_stats(stats: torch.Tensor, kind: str, what: str) -> tuple[int, int]:
+    _cuda(stats, torch.float64, "stats")
+    if stats.ndim != 3 or stats.shape[2] != 6:
+        raise ValueError(f"{what}: stats must be [G, V, 6], got {tuple(stats.shape)}")
+    if kind not in REGRESSION_KINDS:
+        raise ValueError(f"{what}: kind must be one of {sorted(REGRESSION_KINDS)}, got {kind!r}")
+    return stats.shape[0], stats.shape[1]
+
+
+def regression_from_stats(stats: torch.Tensor, kind: str) -> torch.Tensor:
+    """Raw per-output scores f32 [G, V] of the statistics (computed in f64, rounded once)."""
+    G, V = _regression_stats(stats, kind, "regression_from_stats")
+    out = torch.empty(G, V, dtype=torch.float32, device=stats.device)
+    check(lib().tribe_regression_from_stats(stats.data_ptr(), G, V, REGRESSION_KINDS[kind], out.data_ptr(), _stream()),
+          "tribe_regression_from_stats")
+    return out
+
+
+def regression_reduce(stats: torch.Tensor, kind: str, mode: str) -> torch.Tensor:
+    """One f64 score per group [G]: 'pooled' (mse / rmse / mae over every element), 'uniform_average' or 'variance_weighted' over the
+    outputs.  The sums run in a fixed order: equal statistics give equal bits."""
+    G, V = _regression_stats(stats, kind, "regression_reduce")
+    if mode not in REGRESSION_MODES:
+        raise ValueError(f"regression_reduce: mode must be one of {sorted(REGRESSION_MODES)}, got {mode!r}")
+    if mode == "pooled" and kind not in ("mse", "rmse", "mae"):
+        raise ValueError(f"regression_reduce: 'pooled' is defined for mse, rmse and mae, not {kind!r}")
+    out = torch.empty(G, dtype=torch.float64, device=stats.device)
+    check(lib().tribe_regression_reduce(stats.data_ptr(), G, V, REGRESSION_KINDS[kind], REGRESSION_MODES[mode], out.data_ptr(), _stream()),
+          "tribe_regression_reduce")
+    return out
+
+
+# --------------------------------------------------------------------------------------
 # retrieval metrics Rank / TopkAcc (csrc/metrics.hip)
 # --------------------------------------------------------------------------------------
 _NORM_KINDS = {None: 0, "x": 1, "y": 2, "xy": 3}

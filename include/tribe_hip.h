@@ -499,6 +499,27 @@ int tribe_retrieval_scores(const float* x, int64_t ldx, const float* y, int64_t 
                            const float* x_norm, const float* y_norm, int32_t norm_kind, float* scores, void* stream);
 /* out[0..4) = {mean, unbiased std, lower median, mean(ranks < topk)} of ranks[0..n) (ranks >= 0), one launch */
 int tribe_rank_reduce(const float* ranks, int64_t n, float topk, float* out, void* stream);
+/* Regression metrics MeanSquaredError / MeanAbsoluteError / R2Score / ExplainedVariance (modeling_utils/metrics/regression.py), plain
+ * and per group.  No workspace.  stats_update takes the arguments of tribe_pearson_stats_update and accumulates, with d = true - pred
+ * formed in f64:   stats[g][v][0..5] += {sum d, sum d^2, sum |d|, sum t, sum t^2, count}
+ * (direct residual sums: the Pearson moments cancel for a prediction that follows its target on an offset, and hold no sum |d|). */
+int tribe_regression_stats_update(const float* pred, const float* truth, int64_t B, int64_t V, int64_t T,
+                                  int64_t sb, int64_t sv, int64_t st, const int64_t* group, int64_t n_groups, double* stats,
+                                  void* stream);
+enum tribe_regression_kind {
+  TRIBE_REGRESSION_MSE = 0, TRIBE_REGRESSION_RMSE = 1, TRIBE_REGRESSION_MAE = 2, TRIBE_REGRESSION_R2 = 3,
+  TRIBE_REGRESSION_EXPLAINED_VARIANCE = 4
+};
+enum tribe_regression_mode { TRIBE_REGRESSION_POOLED = 0, TRIBE_REGRESSION_UNIFORM_AVERAGE = 1, TRIBE_REGRESSION_VARIANCE_WEIGHTED = 2 };
+/* out[g][v] (f32, computed in f64 and rounded once) with n = count, rss = sum d^2, tss = sum t^2 - (sum t)^2 / n and
+ * vres = sum d^2 - (sum d)^2 / n, each centred sum 0 when within n ulps of its raw sum of squares (as the Pearson finaliser):
+ *   mse rss / n;  rmse sqrt(mse);  mae sum |d| / n;  r2 1 - rss / tss;  explained_variance 1 - vres / tss.
+ * tss == 0: 1 when the numerator is 0, else 0 (scikit-learn's force_finite).  n == 0: NaN; r2 with n < 2: NaN. */
+int tribe_regression_from_stats(const double* stats, int64_t n_groups, int64_t V, int32_t kind, float* out, void* stream);
+/* out[g] (f64), one workgroup per group, sums added in a fixed order (equal stats give equal bits):
+ *   pooled (mse, rmse, mae only): sum_v rss / sum_v n (then sqrt), sum_v sum |d| / sum_v n;
+ *   uniform_average: mean_v score_v;  variance_weighted: sum_v tss_v score_v / sum_v tss_v, the uniform average when every tss_v is 0. */
+int tribe_regression_reduce(const double* stats, int64_t n_groups, int64_t V, int32_t kind, int32_t mode, double* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Backward building blocks (pl_module.training_step: loss.backward() of the path).
