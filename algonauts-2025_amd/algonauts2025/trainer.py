@@ -7,6 +7,13 @@ of this build (and loggers, checkpoints, early stopping and progress bars are co
 epoch / step / hook ordering only, with the MI355X pieces plugged in -- HipAdam (one launch per step), GradReducer (bucketed
 RCCL all-reduce overlapped with backward, one process per GPU) and the HIP weight-averaging kernel behind the SWA callback.
 Callbacks receive `(trainer, pl_module)` exactly as Lightning passes them.
+
+`gradient_clip_val` / `gradient_clip_algorithm` carry Lightning's names and documented meaning (`"norm"`: the global L2 norm of all
+gradients of the optimiser is clipped to the value with torch's `clip_grad_norm_` rule; `"value"`: every gradient element is clamped to
+[-value, value]; `None` or a value <= 0: no clipping).  Lightning is not installed here: this is restated from its documentation and
+is "parity unpinned", like `StochasticWeightAveraging`.  Clipping runs after `GradReducer.finish()`, i.e. on the averaged gradients, so
+every rank computes the same coefficient.  With `HipAdam` the norm is one streaming read (tribe_grad_norm), its coefficient stays on
+the device and the optimiser kernel applies it as it loads each gradient (tribe_adam_step_clipped): `p.grad` is not rewritten.
 """
 
 from __future__ import annotations
@@ -20,9 +27,14 @@ from .distributed import GradReducer, world
 
 class Trainer:
     def __init__(self, max_epochs: int, callbacks: tp.Sequence[tp.Any] = (), limit_train_batches: int | None = None,
-                 device: str | torch.device = "cuda", bucket_bytes: int = 512 << 20, reduce_gradients: bool | None = None) -> None:
+                 device: str | torch.device = "cuda", bucket_bytes: int = 512 << 20, reduce_gradients: bool | None = None,
+                 gradient_clip_val: float | None = None, gradient_clip_algorithm: str = "norm") -> None:
         if max_epochs < 1:
             raise ValueError("max_epochs must be >= 1")
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val is not None and gradient_clip_val > 0 else None
+        self.gradient_clip_algorithm = gradient_clip_algorithm
         self.max_epochs, self.callbacks, self.limit_train_batches = max_epochs, list(callbacks), limit_train_batches
         self.device, self.bucket_bytes = device, bucket_bytes
         self.reduce_gradients = reduce_gradients                # None: whenever the process group has more than one rank
@@ -43,6 +55,25 @@ class Trainer:
     def _n_batches(self, loader: tp.Any) -> int:
         n = len(loader)
         return n if self.limit_train_batches is None else min(n, self.limit_train_batches)
+
+    def _clipped_step(self, opt: torch.optim.Optimizer) -> torch.Tensor | None:
+        """The optimiser step under `gradient_clip_val`; returns the total norm (a tensor, not read here) for "norm"."""
+        from modeling_utils.optim import HipAdam, clip_grad_norm_, clip_grad_value_, hip_clip_eligible
+        from tribe_hip import ops
+
+        params = [p for g in opt.param_groups for p in g["params"]]
+        by_norm = self.gradient_clip_algorithm == "norm"
+        grads = [p.grad for p in params if p.grad is not None]
+        if isinstance(opt, HipAdam) and hip_clip_eligible(grads):        # fused: the step's kernel clips as it loads, p.grad stays
+            if by_norm:
+                norm, coef = ops.grad_norm(grads, self.gradient_clip_val, 2.0)
+                opt.step(grad_scale=coef)
+                return norm
+            opt.step(grad_clip_value=self.gradient_clip_val)
+            return None
+        norm = clip_grad_norm_(params, self.gradient_clip_val) if by_norm else clip_grad_value_(params, self.gradient_clip_val)
+        opt.step()
+        return norm
 
     @property
     def estimated_stepping_batches(self) -> int:
@@ -65,7 +96,7 @@ class Trainer:
             self.current_epoch = epoch
             module.train()
             self._call("on_train_epoch_start", module)
-            total, count = 0.0, 0
+            total, count, grad_norm = 0.0, 0, None
             for i, batch in enumerate(train_loader):
                 if i >= self._n_batches(train_loader):
                     break
@@ -77,7 +108,10 @@ class Trainer:
                 loss.backward()
                 if self.reducer is not None:
                     self.reducer.finish()
-                opt.step()
+                if self.gradient_clip_val is None:
+                    opt.step()
+                else:
+                    grad_norm = self._clipped_step(opt)
                 if self.lr_scheduler is not None and self.lr_scheduler["interval"] == "step":
                     self.lr_scheduler["scheduler"].step()
                 self.global_step += 1
@@ -86,6 +120,8 @@ class Trainer:
                 self.lr_scheduler["scheduler"].step()
             self._call("on_train_epoch_end", module)
             record = {"epoch": epoch, "train/loss": total / max(1, count), "lr": opt.param_groups[0]["lr"]}
+            if grad_norm is not None:
+                record["grad_norm"] = float(grad_norm)                 # the last step's total norm: the one read of the epoch
             if val_loader is not None:
                 module.eval()
                 with torch.no_grad():

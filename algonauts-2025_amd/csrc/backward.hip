@@ -483,16 +483,22 @@ __global__ __launch_bounds__(256) void infonce_dlogits_kernel(const float* __res
 // ---- Adam over a whole parameter group in ONE launch (torch.optim.Adam semantics, defaults.py:126-133) -----------------
 // table[i] = {p, g, m, v, n}; work is cut into chunks of ADAM_CHUNK elements: chunk c belongs to tensor chunk_tensor[c] and
 // starts at element chunk_start[c].  HBM-bound: 16 B read + 12 B written per parameter.
-constexpr int ADAM_CHUNK = 16384;
-__global__ __launch_bounds__(256) void adam_step_kernel(const tribe_adam_tensor* __restrict__ table, const int32_t* __restrict__ chunk_tensor,
-                                                        const int64_t* __restrict__ chunk_start, float lr, float beta1, float beta2, float eps,
-                                                        float weight_decay, float bias_c1, float bias_c2_sqrt, int decoupled) {
+// CLIP: every gradient is replaced on load by clamp(g * grad_coef[0], -clip_value, clip_value) (grad_coef NULL = 1, clip_value <= 0 =
+// no clamp) with tribe_grad_scale's arithmetic (grad_clip.hip), so the clipped step equals that pass followed by the plain step bit for
+// bit and t.g is not written.  Without CLIP the two arguments are unused and the body is the plain step's, instruction for instruction.
+template <bool CLIP>
+__device__ __forceinline__ void adam_step_body(const tribe_adam_tensor* __restrict__ table, const int32_t* __restrict__ chunk_tensor,
+                                               const int64_t* __restrict__ chunk_start, float lr, float beta1, float beta2, float eps,
+                                               float weight_decay, float bias_c1, float bias_c2_sqrt, int decoupled,
+                                               const float* __restrict__ grad_coef, float clip_value) {
   const tribe_adam_tensor t = table[chunk_tensor[blockIdx.x]];
   const int64_t i0 = chunk_start[blockIdx.x];
   const int64_t i1 = (i0 + ADAM_CHUNK < t.n) ? i0 + ADAM_CHUNK : t.n;
   const float step_size = lr / bias_c1;
   const bool vec = (((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0 && (i0 & 3) == 0;
+  const float coef = (CLIP && grad_coef) ? grad_coef[0] : 1.f;
   auto update = [&](float& p, float g, float& m, float& v) {
+    if constexpr (CLIP) g = clip_grad(g, coef, clip_value);
     if (weight_decay != 0.f) {
       if (decoupled) p *= 1.f - lr * weight_decay;           // AdamW
       else g = fmaf(weight_decay, p, g);                      // Adam: L2 term joins the gradient
@@ -529,6 +535,21 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const tribe_adam_tensor*
       if (t.p_bf16) t.p_bf16[i] = f32_to_bf16(t.p[i]);
     }
   }
+}
+
+__global__ __launch_bounds__(256) void adam_step_kernel(const tribe_adam_tensor* __restrict__ table, const int32_t* __restrict__ chunk_tensor,
+                                                        const int64_t* __restrict__ chunk_start, float lr, float beta1, float beta2, float eps,
+                                                        float weight_decay, float bias_c1, float bias_c2_sqrt, int decoupled) {
+  adam_step_body<false>(table, chunk_tensor, chunk_start, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2_sqrt, decoupled, nullptr, 0.f);
+}
+
+__global__ __launch_bounds__(256) void adam_step_clipped_kernel(const tribe_adam_tensor* __restrict__ table,
+                                                                const int32_t* __restrict__ chunk_tensor,
+                                                                const int64_t* __restrict__ chunk_start, float lr, float beta1, float beta2,
+                                                                float eps, float weight_decay, float bias_c1, float bias_c2_sqrt, int decoupled,
+                                                                const float* __restrict__ grad_coef, float clip_value) {
+  adam_step_body<true>(table, chunk_tensor, chunk_start, lr, beta1, beta2, eps, weight_decay, bias_c1, bias_c2_sqrt, decoupled, grad_coef,
+                       clip_value);
 }
 
 // ---- running average of the weights (Lightning StochasticWeightAveraging / torch.optim.swa_utils.AveragedModel's default avg_fn:
@@ -815,6 +836,20 @@ extern "C" int tribe_adam_step(const tribe_adam_tensor* table, const int32_t* ch
   const double c1 = 1.0 - pow((double)beta1, (double)step), c2 = 1.0 - pow((double)beta2, (double)step);
   hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_start, lr, beta1,
                      beta2, eps, weight_decay, (float)c1, (float)sqrt(c2), decoupled);
+  TRIBE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tribe_adam_step_clipped(const tribe_adam_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_start, int64_t n_chunks,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step, int32_t decoupled,
+                                       const float* grad_coef, float clip_value, void* stream) {
+  TRIBE_REQUIRE(table && chunk_tensor && chunk_start, "tribe_adam_step_clipped: null pointer");
+  TRIBE_REQUIRE(n_chunks > 0 && n_chunks < (1ll << 31) && step >= 1, "tribe_adam_step_clipped: need chunks and a 1-based step count");
+  TRIBE_REQUIRE(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "tribe_adam_step_clipped: bad hyper-parameters");
+  TRIBE_REQUIRE(clip_value == clip_value, "tribe_adam_step_clipped: clip_value is NaN");
+  const double c1 = 1.0 - pow((double)beta1, (double)step), c2 = 1.0 - pow((double)beta2, (double)step);
+  hipLaunchKernelGGL(adam_step_clipped_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, chunk_tensor, chunk_start,
+                     lr, beta1, beta2, eps, weight_decay, (float)c1, (float)sqrt(c2), decoupled, grad_coef, clip_value);
   TRIBE_LAUNCH_CHECK();
   return 0;
 }

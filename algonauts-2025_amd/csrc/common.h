@@ -64,6 +64,18 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- optimiser work list (tribe_adam_step, tribe_swa_update, tribe_grad_*) --------------------------
+// elements per chunk = per workgroup; the value tribe_adam_chunk_elems() reports
+constexpr int ADAM_CHUNK = 16384;
+// One gradient under clipping: clamp(g * coef, -clip_value, clip_value), clip_value <= 0 = no clamp.  __fmul_rn keeps the product a
+// rounded f32 of its own wherever it is inlined (hipcc contracts a * b + c into an FMA by default), so the in-place pass and the fused
+// optimiser step see the same bits.  The comparisons are false for NaN: NaN stays NaN, as under torch.clamp.
+__device__ __forceinline__ float clip_grad(float g, float coef, float clip_value) {
+  g = __fmul_rn(g, coef);
+  const float lim = clip_value > 0.f ? clip_value : INFINITY;   // no clamp = a limit nothing exceeds: two selects, no branch
+  return g < -lim ? -lim : (g > lim ? lim : g);
+}
+
 // ---- host-side error plumbing ----------------------------------------------------
 void tribe_set_error(const char* fmt, ...);
 

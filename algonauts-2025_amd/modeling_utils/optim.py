@@ -32,21 +32,21 @@ class HipAdam(torch.optim.Optimizer):
         sig = (gi,) + tuple(p.numel() for p in params)
         hit = self._chunks.get(sig)
         if hit is None:
-            chunk = int(lib().tribe_adam_chunk_elems())
-            owner, start = [], []
-            for i, n in enumerate(sig[1:]):
-                s = np.arange(0, n, chunk, dtype=np.int64)
-                owner.append(np.full(len(s), i, dtype=np.int32))
-                start.append(s)
-            dev = params[0].device
             if len(self._chunks) >= 16:      # parameter subsets change with modality dropout; keep the cache bounded
                 self._chunks.pop(next(iter(self._chunks)))
-            hit = (torch.from_numpy(np.concatenate(owner)).to(dev), torch.from_numpy(np.concatenate(start)).to(dev))
-            self._chunks[sig] = hit
+            hit = self._chunks[sig] = ops.chunk_work_list(sig[1:], params[0].device)
         return hit
 
     @torch.no_grad()
-    def step(self, closure: tp.Callable[[], torch.Tensor] | None = None) -> torch.Tensor | None:
+    def step(self, closure: tp.Callable[[], torch.Tensor] | None = None, *, grad_scale: torch.Tensor | None = None,
+             grad_clip_value: float | None = None) -> torch.Tensor | None:
+        """`grad_scale` (one f32 value on the GPU: the coefficient of `ops.grad_norm`) and `grad_clip_value` clip every gradient as the
+        kernel loads it, g -> clamp(g * grad_scale, +-grad_clip_value) (tribe_adam_step_clipped): bit for bit `ops.grad_scale_` followed
+        by the plain step, but `p.grad` is neither read twice nor written.  With neither, the step is the plain tribe_adam_step."""
+        clipped = grad_scale is not None or grad_clip_value is not None
+        if grad_scale is not None and not (isinstance(grad_scale, torch.Tensor) and grad_scale.is_cuda and grad_scale.dtype == torch.float32
+                                           and grad_scale.numel() == 1):
+            raise ValueError("HipAdam.step: grad_scale must be one f32 value on the GPU (ops.grad_norm returns it)")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -88,9 +88,16 @@ class HipAdam(torch.optim.Optimizer):
                 owner, start = self._work_list(gi, params)
                 table_t = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(params[0].device)
                 keep_alive.append(table_t)
-                check(lib().tribe_adam_step(table_t.data_ptr(), owner.data_ptr(), start.data_ptr(), owner.numel(), float(group["lr"]), float(b1),
-                                            float(b2), float(group["eps"]), float(group["weight_decay"]), step, int(group["decoupled_weight_decay"]),
-                                            ops._stream()), "tribe_adam_step")
+                if clipped:
+                    check(lib().tribe_adam_step_clipped(table_t.data_ptr(), owner.data_ptr(), start.data_ptr(), owner.numel(), float(group["lr"]),
+                                                        float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), step,
+                                                        int(group["decoupled_weight_decay"]), ops._p(grad_scale),
+                                                        0.0 if grad_clip_value is None else float(grad_clip_value), ops._stream()),
+                          "tribe_adam_step_clipped")
+                else:
+                    check(lib().tribe_adam_step(table_t.data_ptr(), owner.data_ptr(), start.data_ptr(), owner.numel(), float(group["lr"]),
+                                                float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), step,
+                                                int(group["decoupled_weight_decay"]), ops._stream()), "tribe_adam_step")
                 # the kernel wrote through raw pointers: tell autograd (and this build's packed-weight caches, which key on
                 # `_version`) that the parameters changed
                 torch.autograd.graph.increment_version(params)
@@ -98,3 +105,50 @@ class HipAdam(torch.optim.Optimizer):
                     on_update(p._version)
             del keep_alive      # torch's caching allocator keeps freed blocks ordered on the launch stream
         return loss
+
+
+def _grads_of(parameters: tp.Any) -> tuple[list[torch.Tensor], list[torch.Tensor]]:
+    parameters = [parameters] if isinstance(parameters, torch.Tensor) else list(parameters)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if any(g.is_sparse for g in grads):
+        raise RuntimeError("gradient clipping does not support sparse gradients")
+    return parameters, grads
+
+
+def hip_clip_eligible(grads: tp.Sequence[torch.Tensor]) -> bool:
+    """The HIP kernels take the gradients as they are: contiguous f32 tensors, all on one GPU."""
+    return bool(grads) and all(g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.device == grads[0].device for g in grads)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters: tp.Any, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False,
+                    foreach: bool | None = None) -> torch.Tensor:
+    """`torch.nn.utils.clip_grad_norm_` (same signature, same rule: g *= min(1, max_norm / (norm + 1e-6)), the total norm returned).
+    Contiguous f32 gradients on one GPU with norm_type 2 or inf go through tribe_grad_norm + tribe_grad_scale: one f64 reduction in a
+    fixed order over all tensors, the coefficient kept on the device, no host synchronisation unless `error_if_nonfinite` asks for the
+    one read it needs.  Anything else (CPU tensors, other dtypes or norm orders, no gradient at all) is torch's own function, unchanged."""
+    parameters, grads = _grads_of(parameters)
+    if not hip_clip_eligible(grads) or float(norm_type) not in (2.0, float("inf")):
+        return torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type, error_if_nonfinite, foreach)
+    norm, coef = ops.grad_norm(grads, max_norm, norm_type)
+    if error_if_nonfinite and not bool(torch.isfinite(norm)):
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be "
+                           "clipped. To disable this error and scale the gradients by the non-finite norm anyway, set "
+                           "`error_if_nonfinite=False`")
+    ops.grad_scale_(grads, coef)
+    return norm
+
+
+@torch.no_grad()
+def clip_grad_value_(parameters: tp.Any, clip_value: float, foreach: bool | None = None) -> None:
+    """`torch.nn.utils.clip_grad_value_`: g = clamp(g, -clip_value, clip_value) in place (NaN stays NaN); tribe_grad_scale for
+    contiguous f32 gradients on one GPU, torch's own function otherwise."""
+    parameters, grads = _grads_of(parameters)
+    if not grads:                    # nothing to clamp (this torch's own function raises on an empty list)
+        return None
+    if not hip_clip_eligible(grads):
+        return torch.nn.utils.clip_grad_value_(parameters, clip_value, foreach)
+    clip_value = float(clip_value)
+    if not clip_value > 0.0:         # tribe_grad_scale reads <= 0 as "no clamp"; torch clamps to [-v, v] whatever v is
+        return torch.nn.utils.clip_grad_value_(parameters, clip_value, foreach)
+    ops.grad_scale_(grads, None, clip_value)

@@ -1206,3 +1206,79 @@ def video_preprocess(frames_u8: torch.Tensor, src_index: tp.Any, crop: int) -> t
                                            w_h.ctypes.data, w_h.shape[1], first_w.ctypes.data, w_w.ctypes.data, w_w.shape[1], mean, std,
                                            out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "tribe_video_preprocess_fwd")
     return out
+
+
+# --------------------------------------------------------------------------------------
+# optimiser work list and gradient clipping (csrc/backward.hip, csrc/grad_clip.hip)
+# --------------------------------------------------------------------------------------
+def chunk_work_list(numels: tp.Sequence[int], device: torch.device) -> tuple[torch.Tensor, torch.Tensor]:
+    """(chunk_tensor int32, chunk_start int64) on `device`: tensor i of numels[i] elements cut into chunks of
+    tribe_adam_chunk_elems() -- the work list of tribe_adam_step, tribe_swa_update and tribe_grad_*."""
+    chunk = int(lib().tribe_adam_chunk_elems())
+    owner, start = [], []
+    for i, n in enumerate(numels):
+        s = _np.arange(0, n, chunk, dtype=_np.int64)
+        owner.append(_np.full(len(s), i, dtype=_np.int32))
+        start.append(s)
+    return torch.from_numpy(_np.concatenate(owner)).to(device), torch.from_numpy(_np.concatenate(start)).to(device)
+
+
+_GRAD_WORK: dict[tuple, tuple[torch.Tensor, torch.Tensor]] = {}
+
+
+def _grad_table(grads: tp.Sequence[torch.Tensor], what: str) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor] | None:
+    """(table bytes, chunk_tensor, chunk_start) over the gradients (g and n filled, the other fields NULL); None when there is no element."""
+    grads = [_cuda(g, torch.float32, f"{what}: gradient") for g in grads]
+    grads = [g for g in grads if g.numel()]
+    if not grads:
+        return None
+    dev = grads[0].device
+    if any(g.device != dev for g in grads):
+        raise ValueError(f"{what}: gradients must live on one GPU")
+    sig = (dev.index,) + tuple(g.numel() for g in grads)
+    work = _GRAD_WORK.get(sig)
+    if work is None:
+        if len(_GRAD_WORK) >= 16:            # parameter subsets change with modality dropout; keep the cache bounded
+            _GRAD_WORK.pop(next(iter(_GRAD_WORK)))
+        work = _GRAD_WORK[sig] = chunk_work_list(sig[1:], dev)
+    table = _np.zeros(len(grads), dtype=_lib.ADAM_TENSOR_DTYPE)
+    table["g"] = [g.data_ptr() for g in grads]
+    table["n"] = sig[1:]
+    return torch.from_numpy(table.view(_np.uint8).reshape(-1)).to(dev), work[0], work[1]
+
+
+def grad_norm(grads: tp.Sequence[torch.Tensor], max_norm: float, norm_type: float = 2.0) -> tuple[torch.Tensor, torch.Tensor]:
+    """(norm, coef), 0-dim f32 on the gradients' device: the L2 (norm_type 2) or max-abs (inf) norm of all `grads` (contiguous f32, one
+    GPU) as one vector, accumulated in f64 in a fixed order, and torch's clip coefficient min(1, max_norm / (norm + 1e-6)).  Nothing is
+    read back: hand `coef` to grad_scale_ or to HipAdam.step(grad_scale=coef)."""
+    norm_type = float(norm_type)
+    if norm_type not in (2.0, _math.inf):
+        raise ValueError(f"grad_norm: norm_type must be 2 or inf on the HIP route, got {norm_type}")
+    built = _grad_table(grads, "grad_norm")
+    if built is None:
+        if not len(grads):
+            raise ValueError("grad_norm: no gradients")
+        out = torch.tensor([0.0, min(1.0, float(max_norm) / 1e-6)], dtype=torch.float32, device=grads[0].device)
+        return out[0], out[1]
+    table, owner, start = built
+    partials = torch.empty(owner.numel(), dtype=torch.float64, device=table.device)
+    out = torch.empty(2, dtype=torch.float32, device=table.device)
+    check(lib().tribe_grad_norm(table.data_ptr(), owner.data_ptr(), start.data_ptr(), owner.numel(), 0 if norm_type == 2.0 else 1,
+                                float(max_norm), partials.data_ptr(), out.data_ptr(), _stream()), "tribe_grad_norm")
+    return out[0], out[1]
+
+
+def grad_scale_(grads: tp.Sequence[torch.Tensor], coef: torch.Tensor | None = None, clip_value: float | None = None) -> None:
+    """In place: g = clamp(g * coef, -clip_value, clip_value) for every g in `grads`.  coef: f32 device scalar (grad_norm's) or None = 1;
+    clip_value None or <= 0 = no clamp.  NaN stays NaN."""
+    built = _grad_table(grads, "grad_scale_")
+    if built is None:
+        return
+    table, owner, start = built
+    if coef is not None:
+        _cuda(coef, torch.float32, "grad_scale_: coef")
+        if coef.numel() != 1 or coef.device != table.device:
+            raise ValueError("grad_scale_: coef must be one f32 value on the gradients' device")
+    check(lib().tribe_grad_scale(table.data_ptr(), owner.data_ptr(), start.data_ptr(), owner.numel(), _p(coef),
+                                 0.0 if clip_value is None else float(clip_value), _stream()), "tribe_grad_scale")
+    torch.autograd.graph.increment_version(list(grads))      # written through raw pointers: version-keyed caches must see it

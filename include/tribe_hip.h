@@ -733,6 +733,32 @@ int tribe_adam_step(const tribe_adam_tensor* table, const int32_t* chunk_tensor,
  * m and v are not touched and may be NULL. */
 int tribe_swa_update(const tribe_adam_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_start, int64_t n_chunks, float weight,
                      void* stream);
+/* ---- gradient clipping in front of the optimiser step (torch.nn.utils.clip_grad_norm_ / clip_grad_value_; Lightning's
+ * Trainer(gradient_clip_val, gradient_clip_algorithm)).  Same table and work list as tribe_adam_step.
+ *
+ * tribe_grad_norm reads table[i].g and table[i].n only (p, m, v, p_bf16 may be NULL).  norm_kind 0: the L2 norm of all gradients taken
+ * as one vector; 1: max |g|.  Every element is widened to f64 (its square is then exact), chunk c is reduced to partials[c] (workspace:
+ * n_chunks doubles, device memory) and one workgroup reduces those, all in a fixed order without atomics: equal inputs give equal bits.
+ * out (two floats, device memory) receives
+ *   out[0] = (float)norm                                   the total norm
+ *   out[1] = (float)min(1, max_norm / (norm + 1e-6))       torch's clip coefficient, formed in f64 and rounded once
+ * A NaN element gives out = {NaN, NaN} for both kinds; an infinite element (and no NaN) gives {inf, 0}; all zeros give {0, 1}.
+ * Nothing is copied to the host. */
+int tribe_grad_norm(const tribe_adam_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_start, int64_t n_chunks, int32_t norm_kind,
+                    double max_norm, double* partials, float* out, void* stream);
+/* In place on the gradients: g = clamp(g * coef[0], -clip_value, clip_value).  Reads table[i].g and table[i].n and WRITES through
+ * table[i].g.  coef: device pointer (tribe_grad_norm's out + 1) or NULL = 1; clip_value <= 0 = no clamp.  The product is rounded to f32
+ * before the clamp; NaN stays NaN (torch.clamp's rule), +-inf clamps to +-clip_value.  With a coefficient of exactly 1 and no clamp
+ * nothing is read or written. */
+int tribe_grad_scale(const tribe_adam_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_start, int64_t n_chunks, const float* coef,
+                     float clip_value, void* stream);
+/* tribe_adam_step (all table fields, p_bf16 included) with every gradient replaced, as it is loaded, by tribe_grad_scale's value of it:
+ * bit for bit the result of tribe_grad_scale followed by tribe_adam_step, without the 8 B per parameter of the in-place pass and with
+ * table[i].g left as it was.  grad_coef: device pointer or NULL = 1; clip_value <= 0 = no clamp.  A NaN coefficient (NaN norm) makes
+ * every updated value NaN, as stepping on NaN gradients does. */
+int tribe_adam_step_clipped(const tribe_adam_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_start, int64_t n_chunks, float lr,
+                            float beta1, float beta2, float eps, float weight_decay, int64_t step, int32_t decoupled, const float* grad_coef,
+                            float clip_value, void* stream);
 
 #ifdef __cplusplus
 }
