@@ -6,6 +6,9 @@ module API (`forward(batch, pool_outputs)`, `aggregate_features`, `transformer_f
 `compute_contrastive_loss`, ...) and the same parameter names, so `state_dict()` keys
 (`projectors.<m>.{weight,bias}`, `predictor.{weights,bias}`, `time_pos_embed`,
 `subject_embed.weight`, `encoder.*`, `contrastive_heads.<m>.*`) interchange with the reference.
+With the extension `projector_hidden_sizes` every projector and contrastive head is the `Mlp` of `MlpConfig(hidden_sizes=...)` (keys
+`projectors.<m>.<i>.{weight,bias}` in torchvision.ops.MLP's order): its hidden blocks run as HIP kernels in front of the same fused
+output product; `None`, the default, is the reference's single Linear and launches exactly what it always did.
 
 Data flow of `forward` (every step a HIP launch through libtribe_hip.so, nothing in torch):
   features [B,L,D,T] --tribe_pack_features--> bf16 [B*T, L*D]          (model.py:146-155)
@@ -30,7 +33,7 @@ from torch import nn
 
 from data_utils.dataloader import SegmentData
 from modeling_utils._pack import PackCache, f32c
-from modeling_utils.models.common import MlpConfig, SubjectLayers
+from modeling_utils.models.common import Mlp, MlpConfig, SubjectLayers
 from modeling_utils.models.transformer import TransformerEncoderConfig
 from tribe_hip import ops
 
@@ -60,6 +63,9 @@ class FmriEncoderConfig(pydantic.BaseModel):
     # training: let the contrastive pass reuse the prediction pass's latents whenever its own dropout draw, the inputs and the
     # parameters coincide (bit-identical loss; False = always re-run the encoder as model.py:228 does)
     share_contrastive_latents: bool = True
+    # hidden sizes of every modality projector and contrastive head (MlpConfig.hidden_sizes): Linear -> LayerNorm -> GELU per size in
+    # front of the output Linear.  None = the reference's single Linear (model.py:61, 64)
+    projector_hidden_sizes: list[int] | None = None
 
     def build(self, feature_dims: dict[str, tuple[int, int] | None], n_outputs: int, n_output_timesteps: int) -> nn.Module:
         return FmriEncoder(feature_dims, n_outputs, n_output_timesteps, config=self)
@@ -83,9 +89,10 @@ class FmriEncoder(nn.Module):
             num_layers, feature_dim = tup
             input_dim = feature_dim * num_layers if config.layer_aggregation == "cat" else feature_dim
             output_dim = hidden // len(feature_dims) if config.feature_aggregation == "cat" else hidden
-            self.projectors[modality] = MlpConfig(norm_layer="layer", activation_layer="gelu", dropout=0.0).build(input_dim, output_dim)
+            mlp = MlpConfig(norm_layer="layer", activation_layer="gelu", dropout=0.0, hidden_sizes=config.projector_hidden_sizes)
+            self.projectors[modality] = mlp.build(input_dim, output_dim)
             if config.contrastive_enabled and modality in config.contrastive_modalities:
-                self.contrastive_heads[modality] = MlpConfig(norm_layer="layer", activation_layer="gelu", dropout=0.0).build(input_dim, hidden)
+                self.contrastive_heads[modality] = mlp.build(input_dim, hidden)
         self.combiner = nn.Identity()
         self.predictor = SubjectLayers(in_channels=hidden, out_channels=n_outputs, n_subjects=config.n_subjects,
                                        average_subjects=False, bias=True)
@@ -115,6 +122,15 @@ class FmriEncoder(nn.Module):
 
     def _packed_linear(self, key: str, lin: nn.Linear) -> tuple[torch.Tensor, torch.Tensor]:
         return self._packs.get(key, [lin.weight, lin.bias], lambda: (ops.pack_weight(f32c(lin.weight)), f32c(lin.bias)))
+
+    @staticmethod
+    def _output_linear(proj: nn.Module, packed: torch.Tensor) -> tuple[torch.Tensor, nn.Linear]:
+        """(bf16 operand, Linear) of a projector's or contrastive head's last product: the packed features and the module itself for
+        the reference's single Linear; with projector_hidden_sizes the hidden blocks (Linear -> LayerNorm -> GELU, HIP) run first and
+        hand over their bf16 [B*T, H_pad] output.  Differentiable where grad is enabled."""
+        if isinstance(proj, Mlp):
+            return proj.hidden_operand(packed), proj.blocks()[1]
+        return packed, proj
 
     def _draw_modality_dropout(self) -> list[str]:
         # model.py:133-141 -- same RNG consumption order as the reference
@@ -168,8 +184,9 @@ class FmriEncoder(nn.Module):
                 feat = data[modality]
                 if feat.ndim not in (3, 4):
                     raise AssertionError(f"expected [B, L, D, T] or [B, D, T] features, got {tuple(feat.shape)}")
-                packed = self._pack(feat)
-                w, b = self._packed_linear(f"proj.{modality}", self.projectors[modality])
+                with torch.no_grad():
+                    packed, lin = self._output_linear(self.projectors[modality], self._pack(feat))
+                w, b = self._packed_linear(f"proj.{modality}", lin)
                 ops.projector_fwd(packed, T, w, b, n_out, x, col0, accumulate=(not cat and not first), pos_embed=emb[0],
                                   subj_embed=emb[1], subject_id=emb[2])
             first = False
@@ -246,9 +263,11 @@ class FmriEncoder(nn.Module):
             if m not in self.projectors or m in dropped:  # model.py:143-144,158-159: zero block, no gradient
                 slices.append(torch.zeros(B * T, slot, dtype=torch.float32, device=ref.device))
                 continue
-            packed = self._pack(data[m])
-            lin = self.projectors[m]
-            slices.append(ag.ProjectorFuse.apply(packed, lin.weight, lin.bias))
+            packed, lin = self._output_linear(self.projectors[m], self._pack(data[m]))
+            if lin is self.projectors[m]:
+                slices.append(ag.ProjectorFuse.apply(packed, lin.weight, lin.bias))
+            else:   # behind hidden blocks the operand needs its gradient
+                slices.append(ag.Linear.apply(packed, lin.weight, lin.bias, None, None, True))
         if cat:
             x = torch.cat(slices, dim=1).view(B, T, n_mod * slot)   # model.py:161-162
         else:
@@ -321,8 +340,8 @@ class FmriEncoder(nn.Module):
         if feat is None:
             raise KeyError(f"Modality '{modality}' not found in batch.data")
         B, T = feat.shape[0], feat.shape[-1]
-        packed = self._pack(feat)
-        w, b = self._packed_linear(f"chead.{modality}", self.contrastive_heads[modality])
+        packed, lin = self._output_linear(self.contrastive_heads[modality], self._pack(feat))
+        w, b = self._packed_linear(f"chead.{modality}", lin)
         out = torch.empty(B * T, self.hidden, dtype=torch.float32, device=feat.device)
         ops.projector_fwd(packed, T, w, b, self.hidden, out, 0, False, None, None, None)
         return out.view(B, T, -1)
@@ -350,9 +369,11 @@ class FmriEncoder(nn.Module):
             if modality not in self.contrastive_heads or modality not in data:
                 continue
             feat = data[modality]
-            packed = self._pack(feat)
-            head = self.contrastive_heads[modality]
-            lat = ag.ProjectorFuse.apply(packed, head.weight, head.bias)            # f32 [B * T_mod, hidden]
+            packed, head = self._output_linear(self.contrastive_heads[modality], self._pack(feat))
+            if head is self.contrastive_heads[modality]:
+                lat = ag.ProjectorFuse.apply(packed, head.weight, head.bias)        # f32 [B * T_mod, hidden]
+            else:
+                lat = ag.Linear.apply(packed, head.weight, head.bias, None, None, True)
             T_mod = feat.shape[-1]
             if T_mod != T:   # model.py:234-238: adaptive average pool of the modality latents to the brain's time axis
                 lat = lat.view(B, T_mod, -1).transpose(1, 2).contiguous()           # [B, hidden, T_mod]

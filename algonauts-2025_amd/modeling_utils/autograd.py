@@ -113,13 +113,16 @@ def cast_bf16(x: torch.Tensor) -> torch.Tensor:
     if x.dtype == torch.bfloat16:
         return x.contiguous()
     x = x.contiguous()
+    if x.numel() % 4 and x.ndim == 2 and x.dtype == torch.float32:
+        # the vector kernel takes multiples of 4; odd MLP shapes go through the row kernel's element path (no norm, no activation: a cast)
+        return ops.norm_act(x, None, None, 0.0, None, norm=False, ld_out=x.shape[1])[0]
     y = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
     check(lib().tribe_cast_bf16_fwd(x.data_ptr(), x.numel(), y.data_ptr(), _s()), "tribe_cast_bf16_fwd")
     return y
 
 
 class _WeightPacks:
-    """bf16 W [N, K_pad] and W^T [K, N_pad] per (tensor object, version) of an f32 weight; entries die with the tensor
+    """bf16 W [N, K_pad] and W^T [K_pad, N_pad] per (tensor object, version) of an f32 weight; entries die with the tensor
     (temporaries are rebuilt every step, parameters only when they were updated).  An unpadded pack (K % 64 == 0: a plain element-wise
     cast) is registered as the parameter's bf16 shadow (modeling_utils/shadow.py): HipAdam's kernel then writes it while it updates the
     parameter and `_refreshed` records the new version -- no cast pass after the step; W^T is re-derived from the bf16 pack."""
@@ -148,6 +151,10 @@ class _WeightPacks:
             N, K = wd.shape
             ref = weakref.ref(w, lambda _r, k=key: self._c.pop(k, None))
             hit = [ref, sig, ops.pack_weight(wd), transpose_bf16(wd, 1, N, K, 0, K)[0]]
+            if hit[2].shape[1] != K:
+                # a Linear behind K-padded activations (an MLP's hidden width that is no multiple of 64): its dgrad GEMM produces all
+                # K_pad columns of dx and reads as many rows of W^T -- the rows past K are zeros, like the pad columns of the pack
+                hit[3] = torch.cat([hit[3], hit[3].new_zeros(hit[2].shape[1] - K, hit[3].shape[1])])
             self._c[key] = hit
             if hit[2].shape == wd.shape and w.is_contiguous() and isinstance(w, torch.nn.Parameter):
                 shadow.register(w, hit[2], lambda version, k=key, r=ref: self._refreshed(k, r, version))
@@ -702,6 +709,7 @@ class ProjectorFuse(torch.autograd.Function):
         y = torch.empty(M, N, dtype=torch.float32, device=feat.device)
         _gemm(feat, wp, y, lda=Kp, ldb=Kp, ldc=N, M=M, N=N, K=Kp, bias=b, role=ROLE["projector"])
         ctx.save_for_backward(feat, w)
+        ctx.has_b = b is not None
         return y
 
     @staticmethod
@@ -713,7 +721,47 @@ class ProjectorFuse(torch.autograd.Function):
         dyb = cast_bf16(dy)
         dw = torch.empty(N, Kp, dtype=torch.float32, device=feat.device)
         wgrad(dyb, feat, dw, M, N, Kp, N, Kp)
-        return None, dw[:, :K].contiguous() if Kp != K else dw, colsum(dy, M, N)
+        return None, dw[:, :K].contiguous() if Kp != K else dw, colsum(dy, M, N) if ctx.has_b else None
+
+
+class NormAct(torch.autograd.Function):
+    """y = act(LayerNorm(z)) (norm=False: act(z)) between two Linear layers of an MLP: z f32 [M, N] (a Linear's output) -> bf16
+    [M, N_pad64], pad columns zero: the next Linear's operand as it stands.  One row kernel each way (tribe_norm_act_fwd / _bwd); the
+    backward takes the next Linear's bf16 dx and hands back f32 dz, dgamma and dbeta (fixed-order column sums)."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, eps: float, act: str | None, norm: bool):
+        z = z.contiguous()
+        y, mean, rstd = ops.norm_act(z, gamma, beta, eps, act, norm=norm, want_stats=True)
+        ctx.save_for_backward(z, mean, rstd, gamma, beta)
+        ctx.act, ctx.norm = act, norm
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, mean, rstd, gamma, beta = ctx.saved_tensors
+        want = ctx.norm and (gamma is not None or beta is not None) and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        dz, dgamma, dbeta = ops.norm_act_bwd(dy if dy.stride(-1) == 1 else dy.contiguous(), z, mean, rstd, gamma, beta, ctx.act, norm=ctx.norm,
+                                             param_grads=want)
+        return dz, dgamma if gamma is not None else None, dbeta if beta is not None else None, None, None, None
+
+
+class PackRows(torch.autograd.Function):
+    """x [M, K] (f32 or bf16) -> the bf16 [M, K_pad64] GEMM operand: f32 through tribe_pack_weight_bf16 (row-wise cast + zero padding), bf16
+    as it lies when K % 64 == 0, else through tribe_pack_features with T = 1; the backward hands the leading K columns of the operand's
+    gradient back in x's dtype."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.k, ctx.dtype = x.shape[1], x.dtype
+        x = x.contiguous()
+        if x.dtype == torch.float32:
+            return ops.pack_weight(x)
+        return x if x.shape[1] % 64 == 0 else ops.pack_features(x.unsqueeze(-1), layer_mean=False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy[:, : ctx.k].to(ctx.dtype)
 
 
 _ = tp

@@ -4,8 +4,18 @@ API mirror of /root/reference/modeling_utils/modeling_utils/models/common.py:
   * `SubjectLayers(in_channels, out_channels, n_subjects, bias, init_id, average_subjects)`
     with parameters `weights [S, C, D]`, `bias [S, D]` and `forward(x[B, C, T], subjects) -> [B, D, T]`
     (common.py:14-71);
-  * `MlpConfig(...).build(input_size, output_size)` (common.py:86-141) -- on the hot path
-    `hidden_sizes` is None and it returns a bare `nn.Linear` (common.py:124-128).
+  * `MlpConfig(...).build(input_size, output_size)` (common.py:86-141) -- on the default path
+    `hidden_sizes` is None and it returns a bare `nn.Linear` (common.py:124-128); with hidden sizes it returns `Mlp`, an
+    `nn.Sequential` of stock torch modules in the layout of the `torchvision.ops.MLP` the reference returns (common.py:130-141):
+    per hidden size Linear, norm (if set), activation, Dropout; then the last Linear and a Dropout.  The layout is restated from
+    torchvision's source (torchvision is not a dependency): `state_dict()` keys `0.weight, 0.bias, 1.weight, 1.bias, 4.weight, ...`
+    with a norm and `0.*, 3.*, ...` without one.  `Mlp.forward` runs LayerNorm / GELU, ReLU, ELU, identity blocks on the GPU through
+    HIP (bf16 MFMA GEMM per Linear, tribe_norm_act_fwd / _bwd in between) and everything else through the stock modules.
+
+Two deliberate differences from the reference's `MlpConfig.build`:
+  * the reference appends `output_size` to the config's own `hidden_sizes` list on every call (common.py:131-132), so a second
+    `build` of the same config grows the network; here `build` leaves the config as it is;
+  * `norm_layer="unit"` is a KeyError inside the reference's build (its table has no such entry); here it is a ValueError.
 
 Differences that do not change results: the reference gathers one [C, D] weight copy per
 sample (`index_select`, common.py:61) and runs a batched einsum; here one grouped MFMA GEMM
@@ -114,7 +124,81 @@ class MlpConfig(pydantic.BaseModel):
             assert output_size is not None, "output_size cannot be None if hidden_sizes is empty."
             # parameter holder; FmriEncoder runs it through tribe_projector_fwd
             return nn.Linear(input_size, output_size)
-        raise NotImplementedError(
-            "MlpConfig with hidden_sizes builds torchvision.ops.MLP in the reference (common.py:130-141); "
-            "that branch is never reached from algonauts2025/model.py and is outside the HIP hot path."
-        )
+        if self.norm_layer not in _NORMS:
+            raise ValueError(f"MlpConfig: norm_layer={self.norm_layer!r} has no module (the reference raises KeyError here)")
+        sizes = list(self.hidden_sizes) + ([output_size] if output_size is not None else [])   # a copy: the config is not mutated
+        norm, act = _NORMS[self.norm_layer], _ACTIVATIONS[self.activation_layer]
+        layers: list[nn.Module] = []
+        width = input_size
+        for h in sizes[:-1]:
+            layers.append(nn.Linear(width, h, bias=self.bias))
+            if norm is not None:
+                layers.append(norm(h))
+            layers += [act(), nn.Dropout(self.dropout)]
+            width = h
+        layers += [nn.Linear(width, sizes[-1], bias=self.bias), nn.Dropout(self.dropout)]
+        return Mlp(layers, self.norm_layer, self.activation_layer, self.dropout)
+
+
+_NORMS: dict[str | None, tp.Any] = {"layer": nn.LayerNorm, "batch": nn.BatchNorm1d, "instance": nn.InstanceNorm1d, None: None}
+_ACTIVATIONS: dict[str | None, tp.Any] = {"relu": nn.ReLU, "gelu": nn.GELU, "elu": nn.ELU, "prelu": nn.PReLU, None: nn.Identity}
+
+
+class Mlp(nn.Sequential):
+    """What `MlpConfig.build` returns for a non-empty `hidden_sizes`: stock modules in torchvision.ops.MLP's order (see the module
+    docstring), so parameters, `state_dict()` and the CPU forward are those of the reference's module.
+
+    forward(x[..., in], f32 or bf16) -> f32 [..., out] has two routes:
+      * HIP: x on the GPU, norm None or "layer", activation relu / gelu / elu / None, dropout inactive (p == 0 or eval mode).  Every
+        Linear is the bf16 MFMA GEMM with f32 output, norm + activation one row kernel (modeling_utils.autograd.NormAct); with grad
+        enabled the route is differentiable through the HIP backward kernels.
+      * stock: everything else runs nn.Sequential.forward unchanged (CPU tensors, "batch" / "instance" norms, PReLU, active dropout).
+    `hip_calls` / `stock_calls` count the forwards each route served."""
+
+    def __init__(self, layers: tp.Sequence[nn.Module], norm_layer: str | None, activation_layer: str | None, dropout: float):
+        super().__init__(*layers)
+        self.norm_layer, self.activation_layer, self.dropout = norm_layer, activation_layer, dropout
+        self.hip_calls = self.stock_calls = 0
+
+    def hip_supported(self) -> bool:
+        return (self.norm_layer in (None, "layer") and self.activation_layer in ops.NORM_ACT_ACTS
+                and (self.dropout == 0 or not self.training))
+
+    def blocks(self) -> tuple[list[tuple[nn.Linear, nn.LayerNorm | None]], nn.Linear]:
+        """([(Linear, its LayerNorm or None) per hidden size], the last Linear)."""
+        mods = list(self)
+        linears = [i for i, m in enumerate(mods) if isinstance(m, nn.Linear)]
+        hidden = [(mods[i], mods[i + 1] if isinstance(mods[i + 1], nn.LayerNorm) else None) for i in linears[:-1]]
+        return hidden, mods[linears[-1]]
+
+    def hidden_operand(self, packed: torch.Tensor, input_grad: bool = False) -> torch.Tensor:
+        """The hidden blocks on a packed bf16 [M, K_pad64] input -> the bf16 [M, H_pad64] operand of the last Linear.  input_grad: the
+        input itself needs a gradient (a feature does not: then the first Linear computes none)."""
+        from .. import autograd as ag
+
+        a = packed
+        for i, (lin, norm) in enumerate(self.blocks()[0]):
+            if i == 0 and not input_grad:
+                z = ag.ProjectorFuse.apply(a, lin.weight, lin.bias)
+            else:
+                z = ag.Linear.apply(a, lin.weight, lin.bias, None, None, True)
+            if norm is None:
+                a = ag.NormAct.apply(z, None, None, 0.0, self.activation_layer, False)
+            else:
+                a = ag.NormAct.apply(z, norm.weight, norm.bias, norm.eps, self.activation_layer, True)
+        return a
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not (x.is_cuda and self.hip_supported()):
+            self.stock_calls += 1
+            return super().forward(x)
+        from .. import autograd as ag
+
+        self.hip_calls += 1
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"Mlp: expected an f32 or bf16 input, got {x.dtype}")
+        last = self.blocks()[1]
+        input_grad = torch.is_grad_enabled() and x.requires_grad
+        a = self.hidden_operand(ag.PackRows.apply(x.reshape(-1, x.shape[-1])), input_grad)
+        out = ag.Linear.apply(a, last.weight, last.bias, None, None, True)
+        return out.view(*x.shape[:-1], out.shape[-1])

@@ -18,6 +18,7 @@ LIB_PATH = _HERE / "libtribe_hip.so"
 
 F32, BF16, F64 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SWIGLU, ACT_SILU, ACT_GLU, ACT_GELU_BWD, ACT_EXP2, ACT_MUL_AUX = 0, 1, 2, 3, 4, 5, 6, 7
+ACT_RELU, ACT_ELU = 8, 9   # tribe_norm_act_fwd / tribe_norm_act_bwd only
 BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2
 ROLES = ["generic", "projector", "qkv", "attn_scores", "attn_pv", "out_proj", "ff1", "ff2", "voxel_head", "attention"]
 ROLE = {name: index for index, name in enumerate(ROLES)}   # tribe_gemm_desc.role (and the prof_end slots) by name
@@ -249,6 +250,10 @@ SIGNATURES = {
     "tribe_grad_norm": (C.c_int, [vp, vp, vp, i64, i32, C.c_double, vp, vp, vp]),
     "tribe_grad_scale": (C.c_int, [vp, vp, vp, i64, vp, f32, vp]),
     "tribe_adam_step_clipped": (C.c_int, [vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, i32, vp, f32, vp]),
+    "tribe_norm_act_fwd": (C.c_int, [vp, i64, i64, i64, vp, vp, f32, i32, i32, vp, i32, i64, vp, vp, vp]),
+    "tribe_norm_act_bwd_workspace_bytes": (sz, [i64, i64]),
+    "tribe_norm_act_bwd": (C.c_int, [vp, i32, i64, vp, i64, i64, i64, vp, vp, vp, vp, i32, i32, vp, i32, i64, vp, vp, vp, sz, vp]),
+    "tribe_norm_act_path": (C.c_int, [vp, i64, i64, vp, vp, vp, i32, i64, vp, i32, i64]),
     "tribe_quantize_fp8_fwd": (C.c_int, [vp, i32, i64, i64, i64, f32, vp, i64, vp]),
     "tribe_norm_quantize_fp8_fwd": (C.c_int, [vp, i64, i64, vp, vp, i32, f32, f32, vp, vp]),
     "tribe_absmax_fwd": (C.c_int, [vp, i32, i64, i64, i64, vp, i32, vp]),

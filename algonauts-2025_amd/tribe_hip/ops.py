@@ -343,6 +343,97 @@ def layernorm(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, eps: flo
     return y
 
 
+# hidden block of an MLP: LayerNorm (optional) + activation in one row kernel each way (csrc/mlp.hip)
+NORM_ACT_ACTS = {None: _lib.ACT_NONE, "gelu": _lib.ACT_GELU, "relu": _lib.ACT_RELU, "elu": _lib.ACT_ELU}
+NORM_ACT_PATHS = ("reg4", "reg16", "walk4", "elem")       # tribe_norm_act_path's codes
+
+
+def _row_view(t: torch.Tensor, dtype: torch.dtype | tuple[torch.dtype, ...], name: str, rows: int | None = None,
+              dim: int | None = None) -> tuple[int, int, int]:
+    """(rows, dim, row pitch) of a 2-D tensor whose rows are contiguous (a column slice of a wider buffer is fine)."""
+    _cuda(t, dtype, name, contiguous=False)
+    if t.ndim != 2 or t.shape[0] == 0 or t.shape[1] == 0 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name}: expected a non-empty 2-D tensor with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
+    if (rows is not None and t.shape[0] != rows) or (dim is not None and t.shape[1] < dim):
+        raise ValueError(f"{name}: shape {tuple(t.shape)} does not hold [{rows}, {dim}]")
+    ld = t.stride(0) if t.shape[0] > 1 else t.shape[1]
+    if ld < t.shape[1]:
+        raise ValueError(f"{name}: row pitch {ld} is below the row width {t.shape[1]}")
+    return t.shape[0], t.shape[1], ld
+
+
+def _norm_act_args(what: str, z: torch.Tensor, gamma: torch.Tensor | None, beta: torch.Tensor | None, act: str | None, norm: bool):
+    if act not in NORM_ACT_ACTS:
+        raise ValueError(f"{what}: activation must be one of {list(NORM_ACT_ACTS)}, got {act!r}")
+    rows, dim, ld_z = _row_view(z, torch.float32, "z")
+    if not norm:
+        gamma = beta = None
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is not None:
+            _cuda(t, torch.float32, name)
+            if t.numel() != dim:
+                raise ValueError(f"{what}: {name} must have dim={dim} elements, got shape {tuple(t.shape)}")
+    return rows, dim, ld_z, gamma, beta
+
+
+def norm_act(z: torch.Tensor, gamma: torch.Tensor | None, beta: torch.Tensor | None, eps: float, act: str | None, *, norm: bool = True,
+             out_dtype: torch.dtype = torch.bfloat16, ld_out: int | None = None, out: torch.Tensor | None = None,
+             want_stats: bool = False) -> tuple[torch.Tensor, torch.Tensor | None, torch.Tensor | None]:
+    """(y, mean, rstd): y = act(LayerNorm(z)) (norm=False: act(z)) for z f32 [rows, dim] (row pitch = z.stride(0)) as f32 or bf16
+    [rows, ld_out], columns >= dim zero -- ld_out defaults to dim padded to 64, the K-padded operand of the next GEMM.  `out`: write
+    into this contiguous [rows, ld_out] tensor.  mean / rstd f32 [rows] with want_stats (what the backward needs), else None."""
+    rows, dim, ld_z, gamma, beta = _norm_act_args("norm_act", z, gamma, beta, act, norm)
+    if out is None:
+        out = torch.empty(rows, round_up(dim, 64) if ld_out is None else ld_out, dtype=out_dtype, device=z.device)
+    _cuda(out, (torch.float32, torch.bfloat16), "out")
+    if out.ndim != 2 or out.shape[0] != rows or out.shape[1] < dim:
+        raise ValueError(f"norm_act: out {tuple(out.shape)} does not hold [{rows}, >= {dim}]")
+    mean = torch.empty(rows, dtype=torch.float32, device=z.device) if (want_stats and norm) else None
+    rstd = torch.empty(rows, dtype=torch.float32, device=z.device) if (want_stats and norm) else None
+    check(lib().tribe_norm_act_fwd(z.data_ptr(), rows, dim, ld_z, _p(gamma), _p(beta), eps, int(norm), NORM_ACT_ACTS[act], out.data_ptr(),
+                                   _DT[out.dtype], out.shape[1], _p(mean), _p(rstd), _stream()), "tribe_norm_act_fwd")
+    return out, mean, rstd
+
+
+def norm_act_bwd(dy: torch.Tensor, z: torch.Tensor, mean: torch.Tensor | None, rstd: torch.Tensor | None, gamma: torch.Tensor | None,
+                 beta: torch.Tensor | None, act: str | None, *, norm: bool = True, dz_dtype: torch.dtype = torch.float32,
+                 ld_dz: int | None = None, out: torch.Tensor | None = None,
+                 param_grads: bool = True) -> tuple[torch.Tensor, torch.Tensor | None, torch.Tensor | None]:
+    """(dz, dgamma, dbeta) of norm_act from dy (f32 or bf16, [rows, >= dim] with contiguous rows) and the saved z, mean, rstd.
+    dz f32 or bf16 [rows, ld_dz] (default dim), pad columns zero; dgamma / dbeta f32 [dim] for norm=True with param_grads."""
+    rows, dim, ld_z, gamma, beta = _norm_act_args("norm_act_bwd", z, gamma, beta, act, norm)
+    _, _, ld_dy = _row_view(dy, (torch.float32, torch.bfloat16), "dy", rows, dim)
+    if norm:
+        for name, t in (("mean", mean), ("rstd", rstd)):
+            if t is None or _cuda(t, torch.float32, name).numel() != rows:
+                raise ValueError(f"norm_act_bwd: {name} must be the forward's f32 [{rows}] statistics")
+    if out is None:
+        out = torch.empty(rows, dim if ld_dz is None else ld_dz, dtype=dz_dtype, device=z.device)
+    _cuda(out, (torch.float32, torch.bfloat16), "out")
+    if out.ndim != 2 or out.shape[0] != rows or out.shape[1] < dim:
+        raise ValueError(f"norm_act_bwd: out {tuple(out.shape)} does not hold [{rows}, >= {dim}]")
+    dgamma = dbeta = ws = None
+    nbytes = 0
+    if norm and param_grads:
+        dgamma = torch.empty(dim, dtype=torch.float32, device=z.device)
+        dbeta = torch.empty(dim, dtype=torch.float32, device=z.device)
+        nbytes = lib().tribe_norm_act_bwd_workspace_bytes(rows, dim)
+        ws = workspace(nbytes, z.device, tag="norm_act")
+    check(lib().tribe_norm_act_bwd(dy.data_ptr(), _DT[dy.dtype], ld_dy, z.data_ptr(), rows, dim, ld_z, _p(mean) if norm else None,
+                                   _p(rstd) if norm else None, _p(gamma), _p(beta), int(norm), NORM_ACT_ACTS[act], out.data_ptr(),
+                                   _DT[out.dtype], out.shape[1], _p(dgamma), _p(dbeta), _p(ws), nbytes, _stream()), "tribe_norm_act_bwd")
+    return out, dgamma, dbeta
+
+
+def norm_act_path(z: torch.Tensor, gamma: torch.Tensor | None, beta: torch.Tensor | None, y: torch.Tensor,
+                  dy: torch.Tensor | None = None) -> str:
+    """Name of the row kernel the launcher picks for these tensors (y: the forward's output or the backward's dz)."""
+    _, dim, ld_z = _row_view(z, torch.float32, "z")
+    ld_dy = 0 if dy is None else _row_view(dy, (torch.float32, torch.bfloat16), "dy")[2]
+    return NORM_ACT_PATHS[lib().tribe_norm_act_path(z.data_ptr(), dim, ld_z, _p(gamma), _p(beta), y.data_ptr(), _DT[y.dtype], y.shape[1],
+                                                    _p(dy), 0 if dy is None else _DT[dy.dtype], ld_dy)]
+
+
 def embedding(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     _cuda(table, (torch.float32, torch.bfloat16), "table")
     _cuda(ids, torch.int64, "ids")

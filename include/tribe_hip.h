@@ -45,7 +45,10 @@ enum tribe_act {
   TRIBE_ACT_EXP2 = 6,
   /* ... and with alpha = scale and a row bias of -scale * D[row] (D = rowsum(dO * O)) the dP GEMM writes dS = (alpha * dO.v + bias[row]) * aux[m][n],
    * aux = P (bf16, same layout AND batch strides as C) */
-  TRIBE_ACT_MUL_AUX = 7
+  TRIBE_ACT_MUL_AUX = 7,
+  /* codes of tribe_norm_act_fwd / tribe_norm_act_bwd (which also take NONE and GELU); no GEMM epilogue implements them */
+  TRIBE_ACT_RELU = 8,
+  TRIBE_ACT_ELU = 9     /* alpha = 1 */
 };
 enum tribe_bias_mode { TRIBE_BIAS_NONE = 0, TRIBE_BIAS_COL = 1, TRIBE_BIAS_ROW = 2 };
 /* which operator of the path a GEMM launch serves: selects the kernel SYMBOL (per-operator rows in
@@ -759,6 +762,32 @@ int tribe_grad_scale(const tribe_adam_tensor* table, const int32_t* chunk_tensor
 int tribe_adam_step_clipped(const tribe_adam_tensor* table, const int32_t* chunk_tensor, const int64_t* chunk_start, int64_t n_chunks, float lr,
                             float beta1, float beta2, float eps, float weight_decay, int64_t step, int32_t decoupled, const float* grad_coef,
                             float clip_value, void* stream);
+
+/* ---- hidden block of an MLP (torchvision.ops.MLP layout: Linear -> LayerNorm -> activation), csrc/mlp.hip ----
+ * y = act(u),  u = gamma * (z - mean) * rstd + beta  (norm = 1: nn.LayerNorm over the last axis, biased variance, rstd = 1 / sqrt(var + eps))
+ *              u = z                                  (norm = 0; gamma, beta, eps ignored)
+ * z f32 [rows, dim] with row pitch ld_z; gamma / beta f32 [dim] or NULL (= 1 / 0); act: TRIBE_ACT_NONE, _GELU (erf), _RELU, _ELU.
+ * y f32 or bf16 with row pitch ld_y >= dim; columns dim .. ld_y - 1 are written as zeros (the bf16 form is the K-padded operand of the
+ * next GEMM).  mean / rstd: optional f32 [rows] outputs (norm = 1), the values the arithmetic above used.  The row statistics are f64
+ * sums of the widened inputs, rounded once; the bf16 result is the round-to-nearest-even of the f32 one. */
+int tribe_norm_act_fwd(const float* z, int64_t rows, int64_t dim, int64_t ld_z, const float* gamma, const float* beta, float eps,
+                       int32_t norm, int32_t act, void* y, int32_t y_dtype, int64_t ld_y, float* mean, float* rstd, void* stream);
+/* Backward of the above from dy (f32 or bf16, pitch ld_dy) and the saved z, mean, rstd (norm = 1):
+ *   zh = (z - mean) * rstd, du = dy * act'(u), dzh = du * gamma,
+ *   dz = rstd * (dzh - mean_H(dzh) - zh * mean_H(dzh * zh))   (norm = 0: dz = du), f32 or bf16, pitch ld_dz, pad columns zero;
+ *   dgamma = sum_rows du * zh, dbeta = sum_rows du (f32 [dim], each optional, norm = 1 only).
+ * act': ReLU 0 at u <= 0, ELU exp(u) at u <= 0, GELU Phi(u) + u phi(u).  Row means are f64; the column sums are f64 partials per block
+ * of rows in the workspace (tribe_norm_act_bwd_workspace_bytes), summed in block order by a second launch: no atomics, equal inputs
+ * give equal bits. */
+size_t tribe_norm_act_bwd_workspace_bytes(int64_t rows, int64_t dim);
+int tribe_norm_act_bwd(const void* dy, int32_t dy_dtype, int64_t ld_dy, const float* z, int64_t rows, int64_t dim, int64_t ld_z,
+                       const float* mean, const float* rstd, const float* gamma, const float* beta, int32_t norm, int32_t act, void* dz,
+                       int32_t dz_dtype, int64_t ld_dz, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, void* stream);
+/* Which row kernel the two launchers above pick for these arguments: 0 = row in registers, 4 x 16 bytes per lane (dim <= 1024),
+ * 1 = the same with 16 (dim <= 4096), 2 = 16-byte walk over the row in memory, 3 = element walk (a dim, pitch or pointer that is not
+ * a multiple of four elements).  dy / dz NULL: the forward's choice for (z, y); else the backward's for (dy, z, dz). */
+int tribe_norm_act_path(const float* z, int64_t dim, int64_t ld_z, const float* gamma, const float* beta, const void* y, int32_t y_dtype,
+                        int64_t ld_y, const void* dy, int32_t dy_dtype, int64_t ld_dy);
 
 #ifdef __cplusplus
 }
