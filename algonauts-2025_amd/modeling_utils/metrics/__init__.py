@@ -6,8 +6,9 @@ import pydantic
 from .base import (BaseMetricConfig, GroupedMetric, GroupedMetricConfig, MultidimPearsonCorrCoef,  # noqa: F401
                    MultidimPearsonCorrCoefConfig, OnlinePearsonCorr, TorchMetricConfig)
 from .metrics import OnlinePearsonCorrConfig, Rank, RankConfig, TopkAcc, TopkAccConfig  # noqa: F401
+from .rank_corr import MultidimSpearmanCorrCoef, MultidimSpearmanCorrCoefConfig  # noqa: F401
 from .regression import ExplainedVariance, MeanAbsoluteError, MeanSquaredError, R2Score  # noqa: F401
 
 MetricConfig = tp.Annotated[tp.Union[MultidimPearsonCorrCoefConfig, GroupedMetricConfig, OnlinePearsonCorrConfig, RankConfig,
-                                     TopkAccConfig, TorchMetricConfig],
+                                     TopkAccConfig, TorchMetricConfig, MultidimSpearmanCorrCoefConfig],
                             pydantic.Field(discriminator="name")]

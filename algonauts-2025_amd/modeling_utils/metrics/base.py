@@ -110,6 +110,7 @@ class OnlinePearsonCorr(MultidimPearsonCorrCoef):
         super().reset()
 
 
+# metrics/rank_corr.py adds "MultidimSpearmanCorrCoef" (it imports this module, so the entry is made there)
 _BASE_METRICS = {"MultidimPearsonCorrCoef": MultidimPearsonCorrCoef, "OnlinePearsonCorr": OnlinePearsonCorr}
 
 
@@ -140,7 +141,11 @@ class GroupedMetric(nn.Module):
                 self._ids.append(key)
         slot = torch.tensor([self._index[str(lab)] for lab in labels], dtype=torch.int64, device=preds.device)
         if self._state is None:
-            self._state = _PearsonState(preds.shape[1])
+            # a class that keeps the groups apart itself (rank_corr.py: it holds samples, not moments) is its own state
+            if getattr(self.base_metric_cls, "grouped_state", False):
+                self._state = self.base_metric_cls(**{"num_outputs": preds.shape[1], **self.metric_kwargs})
+            else:
+                self._state = _PearsonState(preds.shape[1])
         if preds.ndim == 1 and self._regression:  # [N]: one output
             preds, target = preds.unsqueeze(-1), target.unsqueeze(-1)
         if preds.ndim == 2:  # [N, V]: every row is its own "batch row" of length T = 1

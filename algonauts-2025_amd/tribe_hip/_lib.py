@@ -287,6 +287,11 @@ SIGNATURES = {
     "tribe_regression_stats_update": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i64, vp, i64, vp, vp]),
     "tribe_regression_from_stats": (C.c_int, [vp, i64, i64, i32, vp, vp]),
     "tribe_regression_reduce": (C.c_int, [vp, i64, i64, i32, i32, vp, vp]),
+    "tribe_rank_append": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, i64, vp, i64, i64, vp, vp, vp, vp, vp]),
+    "tribe_spearman_columns": (C.c_int, [vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
+    "tribe_spearman_workspace_bytes": (sz, [i64, i64, i64]),
+    "tribe_spearman_default_chunk": (i64, []),
+    "tribe_spearman_max_samples": (i64, []),
     "tribe_fbank_workspace_bytes": (sz, [C.POINTER(i64), i32]),
     "tribe_fbank_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, vp, vp, vp, i64, C.POINTER(i32), vp, sz, vp]),
     "tribe_resample_frac_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.POINTER(i64), vp]),

@@ -848,6 +848,104 @@ def rank_reduce(ranks: torch.Tensor, topk: float = 1.0) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------
+# Spearman rank correlation (csrc/rank_corr.hip)
+# --------------------------------------------------------------------------------------
+SPEARMAN_MAX_SAMPLES = 1 << 20   # tribe_spearman_max_samples(): the int64 rank sums are exact up to here
+
+
+def spearman_default_chunk() -> int:
+    """The largest column one workgroup sorts and ranks in LDS (`chunk=0` of spearman_columns)."""
+    return int(lib().tribe_spearman_default_chunk())
+
+
+def rank_append(pred_state: torch.Tensor, true_state: torch.Tensor, counts: torch.Tensor, pred: torch.Tensor, true: torch.Tensor,
+                group: torch.Tensor | None = None) -> None:
+    """Append the samples of pred / true [B, V, T] (any common strides) to the sample state f32 [G, V, capacity]: the T samples of
+    batch row b go behind the counts[group[b]] samples its group holds (group int64 [B], None: group 0), and counts (int64 [G], on
+    the device) advance.  The caller keeps capacity at or above the number of samples it has appended: a row that would not fit is
+    dropped.  No host synchronisation."""
+    _cuda(pred_state, torch.float32, "pred_state")
+    _cuda(true_state, torch.float32, "true_state")
+    _cuda(counts, torch.int64, "counts")
+    _cuda(pred, torch.float32, "pred", contiguous=False)
+    _cuda(true, torch.float32, "true", contiguous=False)
+    B, V, T, sb, sv, st = _bvt_strides(pred, true, "rank_append")
+    G, cap = pred_state.shape[0], pred_state.shape[-1]
+    if pred_state.shape != (G, V, cap) or true_state.shape != (G, V, cap) or counts.shape != (G,):
+        raise ValueError(f"rank_append: states must be [G, {V}, capacity] and counts [G], got {tuple(pred_state.shape)} / "
+                         f"{tuple(true_state.shape)} / {tuple(counts.shape)}")
+    if B == 0 or T == 0:
+        return
+    if group is not None:
+        _cuda(group, torch.int64, "group")
+        if group.numel() != B:
+            raise ValueError("rank_append: group must have B entries")
+    positions = torch.empty(B, dtype=torch.int64, device=pred.device)
+    check(lib().tribe_rank_append(pred.data_ptr(), true.data_ptr(), B, V, T, sb, sv, st, _p(group), G, cap, counts.data_ptr(),
+                                  positions.data_ptr(), pred_state.data_ptr(), true_state.data_ptr(), _stream()), "tribe_rank_append")
+
+
+def _spearman_state(pred_cols: torch.Tensor, true_cols: torch.Tensor, n: int, chunk: int, want_ranks: bool
+                    ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor | None, torch.Tensor | None]:
+    """Columns as the state holds them: f32 [V, ld] with the first n of every row filled."""
+    V, ld = pred_cols.shape
+    if n > SPEARMAN_MAX_SAMPLES:
+        raise ValueError(f"spearman: {n} samples in one group exceed 2^20")
+    dev = pred_cols.device
+    rho = torch.empty(V, dtype=torch.float32, device=dev)
+    sums = torch.empty(V, 3, dtype=torch.int64, device=dev)
+    rp = torch.empty(V, n, dtype=torch.float32, device=dev) if want_ranks else None
+    rt = torch.empty(V, n, dtype=torch.float32, device=dev) if want_ranks and true_cols is not pred_cols else None
+    ws = workspace(lib().tribe_spearman_workspace_bytes(n, V, chunk), dev, "spearman")
+    check(lib().tribe_spearman_columns(pred_cols.data_ptr(), true_cols.data_ptr(), ld, n, V, chunk, rho.data_ptr(), sums.data_ptr(),
+                                       _p(rp), _p(rt), ws.data_ptr(), ws.numel(), _stream()), "tribe_spearman_columns")
+    return rho, sums, rp, rt
+
+
+def spearman_from_state(pred_state: torch.Tensor, true_state: torch.Tensor, n: int, chunk: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """(rho f32 [V], sums int64 [V, 3]) of one group's sample state f32 [V, capacity] (a row of rank_append's state), n samples
+    per column."""
+    _cuda(pred_state, torch.float32, "pred_state")
+    _cuda(true_state, torch.float32, "true_state")
+    if pred_state.ndim != 2 or pred_state.shape != true_state.shape or not 1 <= n <= pred_state.shape[1]:
+        raise ValueError(f"spearman_from_state: states {tuple(pred_state.shape)} / {tuple(true_state.shape)}, n = {n}")
+    return _spearman_state(pred_state, true_state, int(n), int(chunk), False)[:2]
+
+
+def _sample_columns(x: torch.Tensor, y: torch.Tensor, what: str) -> tuple[torch.Tensor, torch.Tensor, int]:
+    """[N, V] matrices -> their [V, N] column-contiguous copies, through the append kernel."""
+    _cuda(x, torch.float32, "x", contiguous=False)
+    _cuda(y, torch.float32, "y", contiguous=False)
+    if x.ndim != 2 or x.shape != y.shape or x.shape[0] == 0 or x.shape[1] == 0:
+        raise ValueError(f"{what}: expected equal non-empty [N, V] matrices, got {tuple(x.shape)} / {tuple(y.shape)}")
+    N, V = x.shape
+    if N > SPEARMAN_MAX_SAMPLES:
+        raise ValueError(f"{what}: {N} samples exceed 2^20")
+    if x.stride() != y.stride():
+        x, y = x.contiguous(), y.contiguous()
+    xs = torch.empty(1, V, N, dtype=torch.float32, device=x.device)
+    ys = torch.empty_like(xs)
+    rank_append(xs, ys, torch.zeros(1, dtype=torch.int64, device=x.device), x.t().unsqueeze(0), y.t().unsqueeze(0))
+    return xs[0], ys[0], N
+
+
+def spearman_columns(x: torch.Tensor, y: torch.Tensor, chunk: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """Spearman's rho of every column of x / y f32 [N, V] (scipy.stats.spearmanr per column, nan_policy "propagate"): (rho f32 [V],
+    sums int64 [V, 3] = {sum a b, sum a^2, sum b^2} of the doubled centred ranks a, b).  chunk: 0 = default; a power of two in
+    [64, spearman_default_chunk()] moves the border between the one-workgroup route (N <= chunk) and the merge route."""
+    xs, ys, N = _sample_columns(x, y, "spearman_columns")
+    return _spearman_state(xs, ys, N, int(chunk), False)[:2]
+
+
+def rank_columns(x: torch.Tensor, chunk: int = 0) -> torch.Tensor:
+    """Average ranks (1-based, ties share the mean of their positions) of every column of x f32 [N, V], as
+    scipy.stats.rankdata(x, "average", axis=0); f32 [N, V] (a transposed view of the [V, N] the kernel writes).  A column with a NaN
+    is NaN."""
+    xs, _, N = _sample_columns(x, x, "rank_columns")
+    return _spearman_state(xs, xs, N, int(chunk), True)[2].t()
+
+
+# --------------------------------------------------------------------------------------
 # measurement hook: HIP events around every GEMM launch, summed per operator role
 # --------------------------------------------------------------------------------------
 def prof_begin(max_records: int = 4096) -> None:

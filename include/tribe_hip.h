@@ -523,6 +523,31 @@ int tribe_regression_from_stats(const double* stats, int64_t n_groups, int64_t V
  *   pooled (mse, rmse, mae only): sum_v rss / sum_v n (then sqrt), sum_v sum |d| / sum_v n;
  *   uniform_average: mean_v score_v;  variance_weighted: sum_v tss_v score_v / sum_v tss_v, the uniform average when every tss_v is 0. */
 int tribe_regression_reduce(const double* stats, int64_t n_groups, int64_t V, int32_t kind, int32_t mode, double* out, void* stream);
+/* Spearman rank correlation per output column (modeling_utils/metrics/rank_corr.py: MultidimSpearmanCorrCoef), csrc/rank_corr.hip.
+ * The sample state is pred_state / truth_state f32 [n_groups][V][capacity]: one contiguous run of samples per (group, column), of
+ * which counts[g] (int64, on the device) are filled.
+ * append: pred / truth are strided [B, V, T] views (the arguments of tribe_pearson_stats_update); the T samples of batch row b go
+ *   behind the samples of group[b] (NULL: group 0) in batch order, and counts[group[b]] += T.  positions: int64 [B] scratch.  A row
+ *   whose group lies outside [0, n_groups) or whose run would pass `capacity` is dropped: the caller, who knows how many rows it
+ *   has appended, keeps capacity at or above that.  No host synchronisation. */
+int tribe_rank_append(const float* pred, const float* truth, int64_t B, int64_t V, int64_t T, int64_t sb, int64_t sv, int64_t st,
+                      const int64_t* group, int64_t n_groups, int64_t capacity, int64_t* counts, int64_t* positions,
+                      float* pred_state, float* truth_state, void* stream);
+/* Column v holds the n samples pred[v * ld .. + n) / truth[v * ld .. + n), 1 <= n <= tribe_spearman_max_samples() = 2^20.  With
+ * a_i = #{x_j < x_i} + #{x_j <= x_i} - n (= 2 * average rank - (n + 1); -0.0 ties with +0.0, the infinities are ordinary values)
+ * of the predictions and b_i of the targets:
+ *   sums[v][0..3) = {sum a_i b_i, sum a_i^2, sum b_i^2}   (int64: exact, bit-reproducible)
+ *   rho[v] = sums[0] / sqrt((double)sums[1] * (double)sums[2]) clamped to [-1, 1], rounded once to f32; NaN for n < 2, a constant
+ *            column or a NaN among the column's samples (its sums are then 0)
+ *   rank_pred / rank_truth (NULL: not written): the average ranks (1-based) f32 [V][n]; NaN in a column with a NaN.
+ * chunk <= 0: tribe_spearman_default_chunk(); else a power of two in [64, default].  n <= chunk: one workgroup sorts and ranks a column
+ * in LDS (no workspace).  n > chunk: chunks sorted in LDS, merged pairwise through `workspace`
+ * (tribe_spearman_workspace_bytes(n, V, chunk); columns are taken in rounds, so it does not grow with V), ranked by binary search. */
+int tribe_spearman_columns(const float* pred, const float* truth, int64_t ld, int64_t n, int64_t V, int64_t chunk, float* rho,
+                           int64_t* sums, float* rank_pred, float* rank_truth, void* workspace, size_t workspace_bytes, void* stream);
+size_t tribe_spearman_workspace_bytes(int64_t n, int64_t V, int64_t chunk);
+int64_t tribe_spearman_default_chunk(void);
+int64_t tribe_spearman_max_samples(void);
 
 /* ------------------------------------------------------------------------- *
  * Backward building blocks (pl_module.training_step: loss.backward() of the path).
