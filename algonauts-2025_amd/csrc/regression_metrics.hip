@@ -3,106 +3,29 @@
 // the residual sums are taken directly.  The Pearson moments {Sx, Sy, Sxx, Syy, Sxy} cannot serve here: sum |d| has no expression in
 // moments, and sum d^2 = Sxx - 2 Sxy + Syy cancels when the prediction follows the target on an offset (t = 1e3 + N(0, 1),
 // p = t + 1e-3 N(0, 1): the moment form loses 1e-4 .. 1e-2 of the residual sum, the direct sum stays within n ulps).
-// Same addressing, grouping and launch branches as the Pearson statistics of loss.hip; HBM-bound at 8 bytes read per element.
-#include "common.h"
+// Addressing, grouping and launch branches are the shared kernel pair of bvt_stats.h, which the Pearson statistics of loss.hip use too;
+// this file supplies the accumulator and the finalisers.  HBM-bound at 8 bytes read per element.
+#include "bvt_stats.h"
 
 namespace {
 
-// Strided fallback (any st): one workgroup per voxel v; for each row b: 5 sums over t, added into dst[g(b)][v][0..5]
-__global__ __launch_bounds__(256) void regression_stats_strided_kernel(const float* __restrict__ pred, const float* __restrict__ truth,
-                                                                       int64_t B, int64_t V, int64_t T, int64_t sb, int64_t sv, int64_t st,
-                                                                       const int64_t* __restrict__ group, int64_t n_groups,
-                                                                       double* __restrict__ stats) {
-  __shared__ double sh[4];
-  const int64_t v = blockIdx.x;
-  for (int64_t b = 0; b < B; ++b) {
-    const float* x = pred + b * sb + v * sv;
-    const float* y = truth + b * sb + v * sv;
-    double s[5] = {0, 0, 0, 0, 0};
-    for (int64_t t = threadIdx.x; t < T; t += blockDim.x) {
-      const double c = (double)y[t * st], d = c - (double)x[t * st];
-      s[0] += d; s[1] = fma(d, d, s[1]); s[2] += fabs(d); s[3] += c; s[4] = fma(c, c, s[4]);
-    }
-    double r[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) r[k] = block_sum_d(s[k], sh);
-    if (threadIdx.x == 0) {
-      int64_t g = group ? group[b] : 0;
-      if (g >= 0 && g < n_groups) {
-        double* dst = stats + (g * V + v) * 6;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) dst[k] += r[k];
-        dst[5] += (double)T;
-      }
-    }
+// {sum d, sum d^2, sum |d|, sum t, sum t^2} of bvt_stats.h's [G, V, 6] state (x = prediction, y = target, d = y - x)
+struct RegressionAcc {
+  static __device__ __forceinline__ void one(double (&s)[5], const float* x, const float* y, int64_t o) {
+    const double c = (double)y[o], d = c - (double)x[o];
+    s[0] += d; s[1] = fma(d, d, s[1]); s[2] += fabs(d); s[3] += c; s[4] = fma(c, c, s[4]);
   }
-}
-
-// Contiguous rows (st == 1, 16-byte aligned, T % 4 == 0) -- the layout the voxel head writes.  Workgroup (v, chunk) owns voxel v of
-// `rows_per_wg` consecutive sequences; each of its four waves walks whole rows (float4 per lane and tensor, four pairs requested before
-// the first is used) and keeps the five f64 sums in registers across rows of the same group; only a change of group (grouped metric:
-// one state per subject) or the end of the chunk costs a wave reduction and six vector f64 atomics.  No LDS, no barrier.
-__device__ __forceinline__ void regression_flush(double (&s)[5], double cnt, double* __restrict__ dst) {
-#pragma unroll
-  for (int k = 0; k < 5; ++k) s[k] = wave_sum_d(s[k]);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) unsafeAtomicAdd(dst + k, s[k]);
-    unsafeAtomicAdd(dst + 5, cnt);
+  static __device__ __forceinline__ void quad(double (&s)[5], const float4& a, const float4& c) {
+    // a = prediction, c = target.  The f32 squares are exact in f64 after widening; d rounds once, d^2 only inside the fma
+    const double cx = c.x, cy = c.y, cz = c.z, cw = c.w;
+    const double dx = cx - (double)a.x, dy = cy - (double)a.y, dz = cz - (double)a.z, dw = cw - (double)a.w;
+    s[0] += (dx + dy) + (dz + dw);
+    s[1] = fma(dx, dx, fma(dy, dy, fma(dz, dz, fma(dw, dw, s[1]))));
+    s[2] += (fabs(dx) + fabs(dy)) + (fabs(dz) + fabs(dw));
+    s[3] += (cx + cy) + (cz + cw);
+    s[4] = fma(cx, cx, fma(cy, cy, fma(cz, cz, fma(cw, cw, s[4]))));
   }
-#pragma unroll
-  for (int k = 0; k < 5; ++k) s[k] = 0.0;
-}
-
-__device__ __forceinline__ void regression_acc4(double (&s)[5], const float4& a, const float4& c) {
-  // a = prediction, c = target.  The f32 squares are exact in f64 after widening; d rounds once, d^2 only inside the fma
-  const double cx = c.x, cy = c.y, cz = c.z, cw = c.w;
-  const double dx = cx - (double)a.x, dy = cy - (double)a.y, dz = cz - (double)a.z, dw = cw - (double)a.w;
-  s[0] += (dx + dy) + (dz + dw);
-  s[1] = fma(dx, dx, fma(dy, dy, fma(dz, dz, fma(dw, dw, s[1]))));
-  s[2] += (fabs(dx) + fabs(dy)) + (fabs(dz) + fabs(dw));
-  s[3] += (cx + cy) + (cz + cw);
-  s[4] = fma(cx, cx, fma(cy, cy, fma(cz, cz, fma(cw, cw, s[4]))));
-}
-
-__global__ __launch_bounds__(256) void regression_stats_rows_kernel(const float* __restrict__ pred, const float* __restrict__ truth,
-                                                                    int64_t B, int64_t V, int64_t T, int64_t sb, int64_t sv,
-                                                                    const int64_t* __restrict__ group, int64_t n_groups,
-                                                                    int64_t rows_per_wg, double* __restrict__ stats) {
-  const int64_t v = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t b0 = (int64_t)blockIdx.y * rows_per_wg;
-  const int64_t b1 = (b0 + rows_per_wg < B) ? b0 + rows_per_wg : B;
-  const int64_t T4 = T >> 2;
-  double s[5] = {0, 0, 0, 0, 0};
-  double cnt = 0.0;
-  int64_t g_cur = -1;
-  for (int64_t b = b0 + wave; b < b1; b += 4) {
-    int64_t g = group ? group[b] : 0;
-    if (g < 0 || g >= n_groups) continue;                       // rows of an unknown group are skipped
-    if (g != g_cur) {
-      if (g_cur >= 0) regression_flush(s, cnt, stats + (g_cur * V + v) * 6);
-      g_cur = g;
-      cnt = 0.0;
-    }
-    const float4* x = (const float4*)(pred + b * sb + v * sv);
-    const float4* y = (const float4*)(truth + b * sb + v * sv);
-    int64_t i = lane;
-    for (; i + 192 < T4; i += 256) {                            // four float4 pairs requested before the first is used
-      float4 a[4], c[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { a[u] = load_nt_f4(x + i + 64 * u); c[u] = load_nt_f4(y + i + 64 * u); }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) regression_acc4(s, a[u], c[u]);
-    }
-    for (; i < T4; i += 64) {
-      const float4 a = load_nt_f4(x + i), c = load_nt_f4(y + i);
-      regression_acc4(s, a, c);
-    }
-    cnt += (double)T;
-  }
-  if (g_cur >= 0) regression_flush(s, cnt, stats + (g_cur * V + v) * 6);
-}
+};
 
 // One voxel's score in f64 (scikit-learn's force_finite=True conventions).  tss and the residual variance use the Pearson finaliser's
 // rule: a centred sum of squares within n ulps of its raw sum of squares counts as 0.
@@ -178,37 +101,13 @@ __global__ __launch_bounds__(256) void regression_reduce_kernel(const double* __
   out[blockIdx.x] = r;
 }
 
-static void launch_regression_stats(const float* pred, const float* truth, int64_t B, int64_t V, int64_t T, int64_t sb, int64_t sv, int64_t st,
-                                    const int64_t* group, int64_t n_groups, double* stats, hipStream_t s) {
-  const bool rows = st == 1 && T % 4 == 0 && sb % 4 == 0 && sv % 4 == 0 && ((uintptr_t)pred % 16) == 0 && ((uintptr_t)truth % 16) == 0 &&
-                    V <= 0x7fffffff;
-  if (!rows) {
-    hipLaunchKernelGGL(regression_stats_strided_kernel, dim3((unsigned)V), dim3(256), 0, s, pred, truth, B, V, T, sb, sv, st, group, n_groups,
-                       stats);
-    return;
-  }
-  // >= ~4096 workgroups when the batch allows it (256 CUs x 8 resident), at least 4 rows (one per wave) per workgroup
-  int64_t chunks = (4096 + V - 1) / V;
-  const int64_t max_chunks = (B + 3) / 4;
-  if (chunks > max_chunks) chunks = max_chunks;
-  if (chunks < 1) chunks = 1;
-  if (chunks > 65535) chunks = 65535;
-  const int64_t rows_per_wg = (B + chunks - 1) / chunks;
-  chunks = (B + rows_per_wg - 1) / rows_per_wg;
-  hipLaunchKernelGGL(regression_stats_rows_kernel, dim3((unsigned)V, (unsigned)chunks), dim3(256), 0, s, pred, truth, B, V, T, sb, sv, group,
-                     n_groups, rows_per_wg, stats);
-}
-
 }  // namespace
 
 extern "C" int tribe_regression_stats_update(const float* pred, const float* truth, int64_t B, int64_t V, int64_t T, int64_t sb,
                                              int64_t sv, int64_t st, const int64_t* group, int64_t n_groups, double* stats,
                                              void* stream) {
-  TRIBE_REQUIRE(pred && truth && stats, "tribe_regression_stats_update: null pointer");
-  TRIBE_REQUIRE(B > 0 && V > 0 && T > 0 && n_groups > 0, "tribe_regression_stats_update: bad shape B=%lld V=%lld T=%lld groups=%lld",
-                (long long)B, (long long)V, (long long)T, (long long)n_groups);
-  TRIBE_REQUIRE(V <= 0x7fffffff, "tribe_regression_stats_update: V=%lld exceeds the grid", (long long)V);
-  launch_regression_stats(pred, truth, B, V, T, sb, sv, st, group, n_groups, stats, (hipStream_t)stream);
+  if (check_bvt_stats_args("tribe_regression_stats_update", pred, truth, stats, B, V, T, n_groups)) return -1;
+  launch_bvt_stats<RegressionAcc>(pred, truth, B, V, T, sb, sv, st, group, n_groups, stats, (hipStream_t)stream);
   TRIBE_LAUNCH_CHECK();
   return 0;
 }

@@ -28,23 +28,16 @@ from torch import nn
 
 from tribe_hip import ops
 
+from ._state import _BvtStatsState
 from .regression import REGRESSION_METRICS
 
 
-class _PearsonState(nn.Module):
-    def __init__(self, num_outputs: int, n_groups: int = 1):
-        super().__init__()
-        self.num_outputs, self.n_groups = num_outputs, n_groups
-        self.stats: torch.Tensor | None = None  # f64 [G, V, 6], created on first update (device follows the data)
+class _PearsonState(_BvtStatsState):
+    _ops_update = "pearson_stats_update"
 
-    def _ensure(self, device: torch.device, n_groups: int) -> None:
-        if self.stats is None or self.stats.device != device:
-            self.stats = torch.zeros(max(n_groups, self.n_groups), self.num_outputs, 6, dtype=torch.float64, device=device)
-        elif self.stats.shape[0] < n_groups:
-            grown = torch.zeros(n_groups, self.num_outputs, 6, dtype=torch.float64, device=device)
-            grown[: self.stats.shape[0]] = self.stats
-            self.stats = grown
-        self.n_groups = self.stats.shape[0]
+    def __init__(self, num_outputs: int, n_groups: int = 1):
+        super().__init__(n_groups)
+        self.num_outputs = num_outputs
 
     @staticmethod
     def _as_bvt(x: torch.Tensor) -> torch.Tensor:
@@ -54,26 +47,12 @@ class _PearsonState(nn.Module):
             raise ValueError(f"expected [N, V] or [B, V, T], got {tuple(x.shape)}")
         return x.float().t().unsqueeze(0)  # [1, V, N] strided view of the flattened matrix
 
-    def update_bvt(self, preds: torch.Tensor, target: torch.Tensor, group: torch.Tensor | None = None, n_groups: int = 1) -> None:
-        p, t = self._as_bvt(preds), self._as_bvt(target)
-        if p.shape[1] != self.num_outputs:
-            raise ValueError(f"expected {self.num_outputs} outputs, got {p.shape[1]}")
-        self._ensure(p.device, n_groups)
-        ops.pearson_stats_update(self.stats, p, t, group)
-
-    def sync(self, group: tp.Any = None) -> None:
-        import torch.distributed as dist
-
-        if self.stats is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-            dist.all_reduce(self.stats, op=dist.ReduceOp.SUM, group=group)
+    def _check_width(self, width: int) -> None:
+        if width != self.num_outputs:
+            raise ValueError(f"expected {self.num_outputs} outputs, got {width}")
 
     def per_output(self) -> torch.Tensor:
-        if self.stats is None:
-            raise RuntimeError("compute() called before update()")
-        return ops.pearson_from_stats(self.stats)  # [G, V]
-
-    def reset(self) -> None:
-        self.stats = None
+        return ops.pearson_from_stats(self._require_stats())  # [G, V]
 
 
 class MultidimPearsonCorrCoef(_PearsonState):

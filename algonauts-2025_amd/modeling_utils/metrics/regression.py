@@ -20,37 +20,24 @@ prediction follows the target on an offset, and sum |d| has no moment form).  Th
 
 from __future__ import annotations
 
-import typing as tp
-
 import torch
-from torch import nn
 
 from tribe_hip import ops
+
+from ._state import _BvtStatsState
 
 _MULTIOUTPUT = ("raw_values", "uniform_average", "variance_weighted")
 
 
-class _RegressionState(nn.Module):
-    """f64 [G, V, 6] statistics, created on the first update (device and width follow the data)."""
+class _RegressionState(_BvtStatsState):
+    """The width follows the data: the first update sets it, and subclasses with a declared number of outputs override `_check_width`."""
 
-    def __init__(self, n_groups: int = 1):
-        super().__init__()
-        self.n_groups = n_groups
-        self.stats: torch.Tensor | None = None
-
-    def _check_width(self, width: int) -> None:
-        """Subclasses with a declared number of outputs refuse data of another width."""
+    _ops_update = "regression_stats_update"
 
     def _ensure(self, device: torch.device, width: int, n_groups: int) -> None:
         if self.stats is not None and self.stats.device == device and self.stats.shape[1] != width:
             raise ValueError(f"expected {self.stats.shape[1]} outputs as in the earlier updates, got {width}")
-        if self.stats is None or self.stats.device != device:
-            self.stats = torch.zeros(max(n_groups, self.n_groups), width, 6, dtype=torch.float64, device=device)
-        elif self.stats.shape[0] < n_groups:
-            grown = torch.zeros(n_groups, width, 6, dtype=torch.float64, device=device)
-            grown[: self.stats.shape[0]] = self.stats
-            self.stats = grown
-        self.n_groups = self.stats.shape[0]
+        super()._ensure(device, width, n_groups)
 
     @staticmethod
     def _as_bvt(x: torch.Tensor) -> torch.Tensor:
@@ -62,26 +49,6 @@ class _RegressionState(nn.Module):
         if x.ndim != 2:
             raise ValueError(f"expected [N], [N, V] or [B, V, T], got {tuple(x.shape)}")
         return x.t().unsqueeze(0)  # [1, V, N] strided view of the flattened matrix
-
-    def update_bvt(self, preds: torch.Tensor, target: torch.Tensor, group: torch.Tensor | None = None, n_groups: int = 1) -> None:
-        p, t = self._as_bvt(preds), self._as_bvt(target)
-        self._check_width(p.shape[1])
-        self._ensure(p.device, p.shape[1], n_groups)
-        ops.regression_stats_update(self.stats, p, t, group)
-
-    def sync(self, group: tp.Any = None) -> None:
-        import torch.distributed as dist
-
-        if self.stats is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
-            dist.all_reduce(self.stats, op=dist.ReduceOp.SUM, group=group)
-
-    def _require_stats(self) -> torch.Tensor:
-        if self.stats is None:
-            raise RuntimeError("compute() called before update()")
-        return self.stats
-
-    def reset(self) -> None:
-        self.stats = None
 
 
 class _RegressionMetric(_RegressionState):

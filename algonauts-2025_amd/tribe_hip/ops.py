@@ -651,21 +651,26 @@ def _bvt_strides(pred: torch.Tensor, true: torch.Tensor, what: str) -> tuple[int
     return B, V, T, sb, sv, st
 
 
-def pearson_stats_update(stats: torch.Tensor, pred: torch.Tensor, true: torch.Tensor, group: torch.Tensor | None = None) -> None:
-    """stats f64 [G, V, 6] += sufficient statistics of pred/true [B, V, T]; group int64 [B] or None."""
+def _bvt_stats_update(what: str, stats: torch.Tensor, pred: torch.Tensor, true: torch.Tensor, group: torch.Tensor | None) -> None:
+    """The checks and the C call of `what` = pearson_stats_update / regression_stats_update (csrc/bvt_stats.h: one kernel pair)."""
     _cuda(stats, torch.float64, "stats")
     _cuda(pred, torch.float32, "pred", contiguous=False)
     _cuda(true, torch.float32, "true", contiguous=False)
-    B, V, T, sb, sv, st = _bvt_strides(pred, true, "pearson_stats_update")
+    B, V, T, sb, sv, st = _bvt_strides(pred, true, what)
     G = stats.shape[0]
     if stats.shape != (G, V, 6):
-        raise ValueError(f"pearson_stats_update: stats must be [G, {V}, 6], got {tuple(stats.shape)}")
+        raise ValueError(f"{what}: stats must be [G, {V}, 6], got {tuple(stats.shape)}")
     if group is not None:
         _cuda(group, torch.int64, "group")
         if group.numel() != B:
-            raise ValueError("pearson_stats_update: group must have B entries")
-    check(lib().tribe_pearson_stats_update(pred.data_ptr(), true.data_ptr(), B, V, T, sb, sv, st, _p(group), G, stats.data_ptr(),
-                                           _stream()), "tribe_pearson_stats_update")
+            raise ValueError(f"{what}: group must have B entries")
+    check(getattr(lib(), f"tribe_{what}")(pred.data_ptr(), true.data_ptr(), B, V, T, sb, sv, st, _p(group), G, stats.data_ptr(), _stream()),
+          f"tribe_{what}")
+
+
+def pearson_stats_update(stats: torch.Tensor, pred: torch.Tensor, true: torch.Tensor, group: torch.Tensor | None = None) -> None:
+    """stats f64 [G, V, 6] += sufficient statistics of pred/true [B, V, T]; group int64 [B] or None."""
+    _bvt_stats_update("pearson_stats_update", stats, pred, true, group)
 
 
 def pearson_from_stats(stats: torch.Tensor) -> torch.Tensor:
@@ -700,19 +705,7 @@ REGRESSION_MODES = {"pooled": 0, "uniform_average": 1, "variance_weighted": 2}  
 def regression_stats_update(stats: torch.Tensor, pred: torch.Tensor, true: torch.Tensor, group: torch.Tensor | None = None) -> None:
     """stats f64 [G, V, 6] += {sum d, sum d^2, sum |d|, sum t, sum t^2, n} of d = true - pred over [B, V, T] views (any common
     strides); group int64 [B] or None."""
-    _cuda(stats, torch.float64, "stats")
-    _cuda(pred, torch.float32, "pred", contiguous=False)
-    _cuda(true, torch.float32, "true", contiguous=False)
-    B, V, T, sb, sv, st = _bvt_strides(pred, true, "regression_stats_update")
-    G = stats.shape[0]
-    if stats.shape != (G, V, 6):
-        raise ValueError(f"regression_stats_update: stats must be [G, {V}, 6], got {tuple(stats.shape)}")
-    if group is not None:
-        _cuda(group, torch.int64, "group")
-        if group.numel() != B:
-            raise ValueError("regression_stats_update: group must have B entries")
-    check(lib().tribe_regression_stats_update(pred.data_ptr(), true.data_ptr(), B, V, T, sb, sv, st, _p(group), G, stats.data_ptr(),
-                                              _stream()), "tribe_regression_stats_update")
+    _bvt_stats_update("regression_stats_update", stats, pred, true, group)
 
 
 def _regression_stats(stats: torch.Tensor, kind: str, what: str) -> tuple[int, int]:

@@ -8,7 +8,9 @@ the timed launches by a fill kernel so the first read is not served from a warm 
 would leave there.  Per kernel: average HIP-event time over 20 launches on the launch stream, ALGORITHMIC bytes (each
 input element read once, each output element written once), GB/s and the fraction of the 8 TB/s HBM3E peak
 (MI355X_MICROARCH.md; ~6.3 TB/s is what a streaming kernel reaches in practice).  Run it under
-`rocprofv3 --kernel-trace --stats` for the per-kernel durations committed under profiles/."""
+`rocprofv3 --kernel-trace --stats` for the per-kernel durations committed under profiles/.  The Pearson statistics run the
+shared kernel pair of csrc/bvt_stats.h (bvt_stats_rows_kernel<PearsonAcc>); the committed profiles list it under its
+earlier name, pearson_stats_rows_kernel (the same ISA)."""
 import json
 import sys
 from pathlib import Path
@@ -64,7 +66,7 @@ def pearson_bwd():
 cases = {
     "mse_fwd (mse_partial_kernel)": (lambda: ops.mse(pred, true), 8 * n),
     "mse_bwd (mse_bwd_kernel)": (mse_bwd, 12 * n),
-    "pearson_stats_update, one group (pearson_stats_rows_kernel)": (lambda: ops.pearson_stats_update(stats1, pred, true), 8 * n),
+    "pearson_stats_update, one group (bvt_stats_rows_kernel<PearsonAcc>)": (lambda: ops.pearson_stats_update(stats1, pred, true), 8 * n),
     "pearson_stats_update, grouped by subject": (lambda: ops.pearson_stats_update(stats4, pred, true, subj), 8 * n),
     "pearson_loss_fwd (stats + final)": (lambda: ops.pearson_loss(pred, true), 8 * n),
     "pearson_loss_bwd (pearson_loss_bwd_kernel)": (pearson_bwd, 12 * n),

@@ -8,11 +8,11 @@ route: HIP-event time of 300 calls after 30 warm-up calls, repeated 5 times with
 the spread (max - min of the 5 repeats) and the algorithmic bytes over the median time as a fraction of the 8 TB/s HBM3E peak.
 
 Routes:
-  regression rows     tribe_regression_stats_update on [B, V, T] contiguous (regression_stats_rows_kernel)
-  pearson rows        tribe_pearson_stats_update on the same tensors (pearson_stats_rows_kernel): same bytes, two fewer f64 operations per
+  regression rows     tribe_regression_stats_update on [B, V, T] contiguous (bvt_stats_rows_kernel<RegressionAcc>)
+  pearson rows        tribe_pearson_stats_update on the same tensors (bvt_stats_rows_kernel<PearsonAcc>): same bytes, two fewer f64 operations per
                       element
-  regression strided  the '(b t) v' matrix viewed as [B, V, T] (regression_stats_strided_kernel)
-  pearson strided     the same view (pearson_stats_strided_kernel)
+  regression strided  the '(b t) v' matrix viewed as [B, V, T] (bvt_stats_strided_kernel<RegressionAcc>)
+  pearson strided     the same view (bvt_stats_strided_kernel<PearsonAcc>)
   torch composed      d = t.double() - p.double(); the five sums over (b, t) with torch reductions
 """
 import statistics

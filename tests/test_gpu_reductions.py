@@ -365,8 +365,8 @@ def test_mse_fwd_bwd(ops, n):
 # ------------------------------------------------------------------------------------------------
 PB = [1, 5, 16, 64, 67]
 PV = [33, 1000, 4097]
-# rows: [B, V, 100] contiguous -> pearson_stats_rows_kernel (+ the float4 loss backward);  t99: [B, V, 99] contiguous and
-# nv: the '(b t) v' matrix viewed as [B, V, 100] (strides (100 V, 1, V)) -> pearson_stats_strided_kernel (+ the scalar backward)
+# rows: [B, V, 100] contiguous -> bvt_stats_rows_kernel<PearsonAcc> (+ the float4 loss backward);  t99: [B, V, 99] contiguous and
+# nv: the '(b t) v' matrix viewed as [B, V, 100] (strides (100 V, 1, V)) -> bvt_stats_strided_kernel<PearsonAcc> (+ the scalar backward)
 LAYOUTS = ["rows", "t99", "nv"]
 G = 4                 # metric groups: rows go to 0 .. G - 2; group G - 1 receives none (n = 0 < 2)
 

@@ -1,9 +1,9 @@
 """GPU: the regression-metric kernels (csrc/regression_metrics.hip), the metric classes on top of them and their use in
 BrainModule, against the float64 restatement of tests/test_regression_metrics_host.py (which scikit-learn pins there).
 
-Launch branches: `rows` ([B, V, 100] contiguous -> regression_stats_rows_kernel), `t99` ([B, V, 99]) and `nv` (the '(b t) v' matrix
-viewed as [B, V, 100], strides (100 V, 1, V)) -> regression_stats_strided_kernel; T = 1028 runs the rows kernel's four-deep loop and
-its remainder.  Rows are split over up to three updates that accumulate; group ids change inside one wave's rows and across row
+Launch branches of the kernel pair that csrc/bvt_stats.h shares with the Pearson statistics: `rows` ([B, V, 100] contiguous ->
+bvt_stats_rows_kernel<RegressionAcc>), `t99` ([B, V, 99]) and `nv` (the '(b t) v' matrix viewed as [B, V, 100], strides (100 V, 1, V))
+-> bvt_stats_strided_kernel<RegressionAcc>; T = 1028 runs the rows kernel's four-deep loop and its remainder.  Rows are split over up to three updates that accumulate; group ids change inside one wave's rows and across row
 chunks, ids -1 / G / G + 3 are skipped and group G - 1 receives nothing.
 
 Bounds (u = 2^-53, k = n + 2 for the n adds behind a sum plus the roundings of d and d^2, on either side; no empirical tolerance):
@@ -223,6 +223,27 @@ def test_one_sample_and_no_group(ops):
         ops.regression_reduce(stats, "r2", "pooled")
     with pytest.raises(ValueError):
         ops.regression_from_stats(stats, "spearman")
+
+
+@pytest.mark.parametrize("B,T,layout", [(3, 99, "t99"), (3, 100, "nv"), (1, 100, "rows"), (1, 1028, "rows")])
+def test_pearson_and_regression_states_walk_the_data_alike(ops, B, T, layout):
+    """Both families run the one kernel pair of csrc/bvt_stats.h, so what they both sum comes out bit for bit equal: the counts,
+    Pearson's Sy (index 1) = regression's sum t (index 3), and Pearson's Syy (index 3) = regression's sum t^2 (index 4; either
+    accumulator adds the exact f64 square of the widened f32 target in one fma).  Only shapes with a fixed summation order: the strided
+    kernel (one workgroup per output adds its rows in order; group 0 receives two of them), and the rows kernel with B = 1, where one
+    wave adds once into a zeroed state (with B > 1 several waves add with atomics in no fixed order)."""
+    V = 5
+    pred, true = regression_data(B, V, T, seed=T + B)
+    gid = torch.tensor([0, 1, 0])[:B].cuda()
+    p, t = _device_view(pred, layout), _device_view(true, layout)
+    pearson, regression = (torch.zeros(2, V, 6, dtype=torch.float64, device="cuda") for _ in range(2))
+    ops.pearson_stats_update(pearson, p, t, gid)
+    ops.regression_stats_update(regression, p, t, gid)
+    want_n = torch.tensor([(B + 1) // 2, B // 2], dtype=torch.float64).mul(T)[:, None].expand(2, V)
+    assert torch.equal(pearson[..., 5].cpu(), want_n) and torch.equal(regression[..., 5], pearson[..., 5]), "sample counts differ"
+    assert torch.equal(pearson[..., 1], regression[..., 3]), "Pearson's Sy and regression's sum t differ in bits"
+    assert torch.equal(pearson[..., 3], regression[..., 4]), "Pearson's Syy and regression's sum t^2 differ in bits"
+    assert (pearson[0, :, 3] > 0).all()
 
 
 # ------------------------------------------------------------------------------------------------

@@ -259,3 +259,39 @@ def test_cpu_tensors_are_refused():
         ops.regression_from_stats(torch.zeros(1, 3, 6, dtype=torch.float64), "mse")
     with pytest.raises(TribeHipError):
         ops.regression_reduce(torch.zeros(1, 3, 6, dtype=torch.float64), "mse", "pooled")
+
+
+@pytest.mark.parametrize("entry", ["tribe_pearson_stats_update", "tribe_regression_stats_update"])
+def test_stats_update_abi_argument_checks(entry):
+    """Both [G, V, 6] update entry points share one argument check (csrc/bvt_stats.h) and refuse bad arguments before any launch (no GPU
+    needed): rc < 0 -> ValueError with the library's message under the entry point's own name."""
+    import ctypes as C
+
+    from tribe_hip._lib import check, lib
+
+    buf = (C.c_float * 64)()
+    p = C.addressof(buf)
+
+    def update(pred=p, truth=p, B=1, V=2, T=4, G=1, stats=p):
+        check(getattr(lib(), entry)(pred, truth, B, V, T, V * T, T, 1, None, G, stats, None), entry)
+
+    for kwargs, message in (({"pred": None}, "null pointer"), ({"truth": None}, "null pointer"), ({"stats": None}, "null pointer"),
+                            ({"B": 0}, "bad shape"), ({"V": 0}, "bad shape"), ({"T": 0}, "bad shape"), ({"G": 0}, "bad shape"),
+                            ({"V": 2**31}, "exceeds the grid")):
+        with pytest.raises(ValueError, match=f"{entry}: .*{message}"):
+            update(**kwargs)
+
+
+def test_pearson_loss_abi_refuses_a_width_beyond_the_grid():
+    """tribe_pearson_loss_fwd launches the same kernel pair, one workgroup column per output: V = 2^31 is refused.  The workspace size
+    is given as the number the entry point asks for (the pointer is never read), so it is the grid check that fires."""
+    import ctypes as C
+
+    from tribe_hip._lib import check, lib
+
+    buf = (C.c_float * 64)()
+    p = C.addressof(buf)
+    V = 2**31
+    with pytest.raises(ValueError, match="tribe_pearson_loss_fwd: .*exceeds the grid"):
+        check(lib().tribe_pearson_loss_fwd(p, p, 1, V, 4, V * 4, 4, 1, 0, p, p, lib().tribe_pearson_loss_workspace_bytes(V), None),
+              "tribe_pearson_loss_fwd")
