@@ -1,5 +1,6 @@
 // Backward building blocks of the TRIBE path (pl_module.training_step -> loss.backward()): streaming kernels only;
-// the dense gradients are MFMA GEMMs (gemm.hip) fed with transposed bf16 operands produced here.  Roofline: HBM.
+// the dense gradients are MFMA GEMMs (gemm.hip) fed with transposed bf16 operands produced here.  Roofline: HBM.  The gradient of the MSE loss (tribe_mse_bwd) is with the other
+// element-wise losses in robust_loss.hip.
 #include "common.h"
 
 namespace {
@@ -327,29 +328,6 @@ __global__ __launch_bounds__(256) void softmax_bwd_reg_kernel(const unsigned sho
     o[2] = f32_to_bf16(pv[j].z * (dv[j].z - delta) * scale); o[3] = f32_to_bf16(pv[j].w * (dv[j].w - delta) * scale);
     *(u16x4_t*)(ds + (lane + 64 * j) * 4) = o;
   }
-}
-
-// dpred = gs * 2 (p - t) / n.  HBM-bound: 12 bytes per element; float4 streams, two pairs in flight per lane.
-__global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ p, const float* __restrict__ t, int64_t n,
-                                                      const float* __restrict__ gs, float* __restrict__ dp, int vec) {
-  const float k = gs[0] * 2.0f / (float)n;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t n4 = vec ? (n >> 2) : 0;
-  const float4* p4 = (const float4*)p;
-  const float4* t4 = (const float4*)t;
-  float4* d4 = (float4*)dp;
-  for (; i + stride < n4; i += 2 * stride) {
-    const float4 a0 = load_nt_f4(p4 + i), b0 = load_nt_f4(t4 + i);
-    const float4 a1 = load_nt_f4(p4 + i + stride), b1 = load_nt_f4(t4 + i + stride);
-    d4[i] = make_float4(k * (a0.x - b0.x), k * (a0.y - b0.y), k * (a0.z - b0.z), k * (a0.w - b0.w));
-    d4[i + stride] = make_float4(k * (a1.x - b1.x), k * (a1.y - b1.y), k * (a1.z - b1.z), k * (a1.w - b1.w));
-  }
-  for (; i < n4; i += stride) {
-    const float4 a = p4[i], b = t4[i];
-    d4[i] = make_float4(k * (a.x - b.x), k * (a.y - b.y), k * (a.z - b.z), k * (a.w - b.w));
-  }
-  for (int64_t j = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) dp[j] = k * (p[j] - t[j]);
 }
 
 __global__ void pool_bwd_kernel(const float* __restrict__ dy, int64_t rows, int64_t T_in, int64_t T_out, float* __restrict__ dx) {
@@ -743,17 +721,6 @@ extern "C" int tribe_softmax_fwd(const float* S, int64_t rows, int64_t T, int64_
   TRIBE_REQUIRE(S && P, "tribe_softmax_fwd: null pointer");
   TRIBE_REQUIRE(rows > 0 && T > 0 && T_pad >= T && ld_s >= T && ld_p >= T_pad, "tribe_softmax_fwd: bad shape");
   return tribe_internal_softmax(S, rows, T, ld_s, P, T_pad, ld_p, (hipStream_t)stream);
-}
-
-extern "C" int tribe_mse_bwd(const float* pred, const float* truth, int64_t n, const float* gscale, float* dpred, void* stream) {
-  TRIBE_REQUIRE(pred && truth && gscale && dpred && n > 0, "tribe_mse_bwd: bad argument");
-  const int vec = ((uintptr_t)pred % 16) == 0 && ((uintptr_t)truth % 16) == 0 && ((uintptr_t)dpred % 16) == 0;
-  int64_t nb = (n / 4 + 511) / 512;
-  if (nb > 4096) nb = 4096;
-  if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(mse_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, pred, truth, n, gscale, dpred, vec);
-  TRIBE_LAUNCH_CHECK();
-  return 0;
 }
 
 extern "C" int tribe_adaptive_avg_pool_bwd(const float* dy, int64_t rows, int64_t T_in, int64_t T_out, float* dx, void* stream) {

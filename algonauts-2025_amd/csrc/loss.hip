@@ -1,4 +1,5 @@
-// Loss / metric reductions on [B, V, T'] predictions and targets (T' contiguous).
+// The Pearson statistics, metric and loss on [B, V, T'] predictions and targets (T' contiguous); the element-wise losses, the
+// default MSE among them, are in robust_loss.hip.
 // pl_module.py:54-56 flattens to [(B T'), V] before the loss; every reduction here is
 // a per-voxel (or global) sum, so the flatten is never materialised: a workgroup owns
 // one voxel of a run of sequences and its waves walk whole rows of T' contiguous floats
@@ -8,54 +9,6 @@
 #include "bvt_stats.h"
 
 namespace {
-
-// HBM-bound: 8 bytes read per element.  Four independent float4 pairs are requested before any is consumed (128 B in
-// flight per lane; 2048 workgroups x 256 lanes cover the ~16 MB the chip needs in flight at 8 TB/s), f32 partial sums of
-// at most 16 squared differences are folded into an f64 carry.
-__global__ __launch_bounds__(256) void mse_partial_kernel(const float* __restrict__ p, const float* __restrict__ t, int64_t n,
-                                                          double* __restrict__ partial) {
-  __shared__ double sh[4];
-  double dacc = 0.0;
-  const int64_t n4 = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const float4* p4 = (const float4*)p;
-  const float4* t4 = (const float4*)t;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + 3 * stride < n4; i += 4 * stride) {
-    float4 a[4], b[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) { a[u] = load_nt_f4(p4 + i + u * stride); b[u] = load_nt_f4(t4 + i + u * stride); }
-    float acc = 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float d0 = a[u].x - b[u].x, d1 = a[u].y - b[u].y, d2 = a[u].z - b[u].z, d3 = a[u].w - b[u].w;
-      acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-    }
-    dacc += (double)acc;
-  }
-  for (; i < n4; i += stride) {
-    const float4 a = p4[i], b = t4[i];
-    const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
-    dacc += (double)(d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3);
-  }
-  float tail = 0.f;
-  for (int64_t j = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
-    const float d = p[j] - t[j];
-    tail += d * d;
-  }
-  dacc += (double)tail;
-  const double tot = block_sum_d(dacc, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(256) void mse_final_kernel(const double* __restrict__ partial, int nparts, int64_t n,
-                                                        float* __restrict__ out) {
-  __shared__ double sh[4];
-  double v = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += blockDim.x) v += partial[i];
-  const double tot = block_sum_d(v, sh);
-  if (threadIdx.x == 0) out[0] = (float)(tot / (double)n);
-}
 
 // The five Pearson moments {Sx, Sy, Sxx, Syy, Sxy} of bvt_stats.h's [G, V, 6] state (x = prediction, y = target)
 struct PearsonAcc {
@@ -110,27 +63,6 @@ __global__ __launch_bounds__(256) void pearson_loss_final_kernel(const double* _
 }
 
 }  // namespace
-
-extern "C" size_t tribe_mse_workspace_bytes(int64_t n) {
-  (void)n;
-  return 2048 * sizeof(double);
-}
-
-extern "C" int tribe_mse_fwd(const float* pred, const float* truth, int64_t n, float* out, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-  TRIBE_REQUIRE(pred && truth && out && workspace, "tribe_mse_fwd: null pointer");
-  TRIBE_REQUIRE(n > 0, "tribe_mse_fwd: empty input");
-  TRIBE_REQUIRE(workspace_bytes >= tribe_mse_workspace_bytes(n), "tribe_mse_fwd: workspace too small");
-  TRIBE_REQUIRE(((uintptr_t)pred % 16) == 0 && ((uintptr_t)truth % 16) == 0, "tribe_mse_fwd: inputs must be 16-byte aligned");
-  int64_t nb = (n / 4 + 1023) / 1024;    // four float4 per lane and trip
-  if (nb > 2048) nb = 2048;              // tribe_mse_workspace_bytes: 2048 partial sums
-  if (nb < 1) nb = 1;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(mse_partial_kernel, dim3((unsigned)nb), dim3(256), 0, s, pred, truth, n, (double*)workspace);
-  hipLaunchKernelGGL(mse_final_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, (int)nb, n, out);
-  TRIBE_LAUNCH_CHECK();
-  return 0;
-}
 
 extern "C" int tribe_pearson_stats_update(const float* pred, const float* truth, int64_t B, int64_t V, int64_t T, int64_t sb,
                                           int64_t sv, int64_t st, const int64_t* group, int64_t n_groups, double* stats,

@@ -584,24 +584,8 @@ class AdaptivePool(torch.autograd.Function):
         return dx, None
 
 
-class MSE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, true):
-        pred, true = pred.contiguous(), true.contiguous()
-        ctx.save_for_backward(pred, true)
-        return ops.mse(pred, true)
-
-    @staticmethod
-    def backward(ctx, g):
-        pred, true = ctx.saved_tensors
-        dp = torch.empty_like(pred)
-        g = upstream_scale(g)
-        check(lib().tribe_mse_bwd(pred.data_ptr(), true.data_ptr(), pred.numel(), g.data_ptr(), dp.data_ptr(), _s()), "tribe_mse_bwd")
-        return dp, None
-
-
 class ElemLoss(torch.autograd.Function):
-    """ops.elem_loss (L1 / SmoothL1 / Huber / MSE, mean | sum) with its HIP backward; no gradient for the target, as in `MSE`."""
+    """ops.elem_loss (L1 / SmoothL1 / Huber / MSE, mean | sum) with its HIP backward; no gradient for the target."""
 
     @staticmethod
     def forward(ctx, pred, true, kind: str, param: float, reduction: str):

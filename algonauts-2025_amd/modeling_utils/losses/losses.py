@@ -128,23 +128,9 @@ class HuberLoss(_ElemLoss):
 
 
 class MSELoss(_ElemLoss):
-    """mean | sum of (pred - true)^2 over all elements (torch.nn.MSELoss).  'mean', the reference's default loss, keeps its own entry
-    points (tribe_mse_fwd / tribe_mse_bwd); 'sum' runs through the element-wise family."""
+    """mean | sum of (pred - true)^2 over all elements (torch.nn.MSELoss); 'mean' is the reference's default loss."""
 
     kind = "mse"
-
-    def forward(self, pred: torch.Tensor, true: torch.Tensor) -> torch.Tensor:
-        if self.reduction != "mean":
-            return super().forward(pred, true)
-        if pred.shape != true.shape:
-            raise ValueError(f"MSELoss: shape mismatch {tuple(pred.shape)} vs {tuple(true.shape)}")
-        if torch.is_grad_enabled() and pred.requires_grad:
-            from ..autograd import MSE
-
-            return MSE.apply(pred.float(), true.float())
-        return ops.mse(pred.float().contiguous(), true.float().contiguous())
-
-    forward_bvt = forward
 
 
 def hip_loss_for(module: nn.Module) -> nn.Module | None:

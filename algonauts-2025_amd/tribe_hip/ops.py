@@ -605,18 +605,6 @@ def adaptive_avg_pool(x: torch.Tensor, t_out: int) -> torch.Tensor:
     return y
 
 
-def mse(pred: torch.Tensor, true: torch.Tensor) -> torch.Tensor:
-    _cuda(pred, torch.float32, "pred")
-    _cuda(true, torch.float32, "true")
-    if pred.shape != true.shape:
-        raise ValueError(f"mse: shape mismatch {tuple(pred.shape)} vs {tuple(true.shape)}")
-    n = pred.numel()
-    out = torch.empty((), dtype=torch.float32, device=pred.device)
-    ws = workspace(lib().tribe_mse_workspace_bytes(n), pred.device, "loss")
-    check(lib().tribe_mse_fwd(pred.data_ptr(), true.data_ptr(), n, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "tribe_mse_fwd")
-    return out
-
-
 ELEM_LOSS_KINDS = {"l1": 0, "smooth_l1": 1, "huber": 2, "mse": 3}        # enum tribe_loss_kind
 ELEM_LOSS_REDUCTIONS = {"mean": 0, "sum": 1}                             # enum tribe_loss_reduction
 

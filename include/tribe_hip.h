@@ -457,14 +457,17 @@ int tribe_adaptive_avg_pool_fwd(const float* x, int64_t rows, int64_t T_in, floa
  * (pl_module.py:54-56 flattens "b d t -> (b t) d"; the reductions below are
  * order-independent so the flatten is never materialised).
  * ------------------------------------------------------------------------- */
-/* nn.MSELoss(): out[0] = mean((pred-true)^2) over all elements (f32 scalar) */
+/* nn.MSELoss(): out[0] = mean((pred-true)^2) over all elements (f32 scalar).  The (TRIBE_LOSS_MSE, TRIBE_REDUCE_MEAN) instance of
+ * tribe_elem_loss_fwd below (the same kernels, the same bits, the same workspace size) behind this entry point's own contract: pred and
+ * truth 16-byte aligned. */
 int tribe_mse_fwd(const float* pred, const float* truth, int64_t n, float* out,
                   void* workspace, size_t workspace_bytes, void* stream);
 size_t tribe_mse_workspace_bytes(int64_t n);
-/* nn.L1Loss / nn.SmoothL1Loss(beta) / nn.HuberLoss(delta) / nn.MSELoss over all n elements of two flat f32 streams (the losses of the
- * run_ensemble.py grid; MSE here serves reduction="sum", the default MSELoss() stays on tribe_mse_fwd).  With d = pred - true:
+/* nn.L1Loss / nn.SmoothL1Loss(beta) / nn.HuberLoss(delta) / nn.MSELoss over all n elements of two flat f32 streams (the default
+ * loss and those of the run_ensemble.py grid).  With d = pred - true:
  *   L1: |d|;  Huber: m (|d| - m / 2), m = min(|d|, delta);  SmoothL1: Huber(beta) / beta, and L1 for beta == 0;  MSE: d^2.
- * param = beta (SmoothL1, >= 0) or delta (Huber, > 0), ignored otherwise.  out[0] = mean | sum (f32 scalar); the partial sums are
+ * param = beta (SmoothL1, >= 0) or delta (Huber, > 0), ignored otherwise.  out[0] = (float)(sum * num / den) in f64, num = 1 / beta
+ * (SmoothL1) | 1, den = n (mean) | 1 (sum); the partial sums are
  * added in a fixed order, so equal inputs give equal bits.  Pointers need 4-byte alignment only (16-byte aligned ones stream float4). */
 enum tribe_loss_kind { TRIBE_LOSS_L1 = 0, TRIBE_LOSS_SMOOTH_L1 = 1, TRIBE_LOSS_HUBER = 2, TRIBE_LOSS_MSE = 3 };
 enum tribe_loss_reduction { TRIBE_REDUCE_MEAN = 0, TRIBE_REDUCE_SUM = 1 };
@@ -575,10 +578,12 @@ int tribe_softmax_bwd(const uint16_t* P, const float* dP, int64_t rows, int64_t 
                       float scale, uint16_t* dS, int64_t ld_ds, void* stream);
 /* row softmax used by the materialised attention of the training path: S f32 [rows, T] -> P bf16 [rows, T_pad] */
 int tribe_softmax_fwd(const float* S, int64_t rows, int64_t T, int64_t ld_s, uint16_t* P, int64_t T_pad, int64_t ld_p, void* stream);
-/* d pred = gscale[0] * 2 / n * (pred - true)   (nn.MSELoss backward) */
+/* d pred = gscale[0] * 2 / n * (pred - true)   (nn.MSELoss backward): tribe_elem_loss_bwd's (TRIBE_LOSS_MSE, TRIBE_REDUCE_MEAN) instance; any
+ * pointer that is not 16-byte aligned selects the scalar form */
 int tribe_mse_bwd(const float* pred, const float* truth, int64_t n, const float* gscale, float* dpred, void* stream);
-/* d pred = gscale[0] * k * d value / d pred of tribe_elem_loss_fwd, k = 1 / n (mean) | 1 (sum):  L1 sign(d) (0 at d == 0),
- * Huber clamp(d, -delta, delta), SmoothL1 clamp(d, -beta, beta) / beta, MSE 2 d.  gscale is a device scalar. */
+/* d pred = gscale[0] * num / den * slope(d), the gradient of tribe_elem_loss_fwd: the factor is formed in f32 from left to right, den = n
+ * (mean) | 1 (sum), num = 1 / beta (SmoothL1) | 2 (MSE) | 1;  slope: L1 sign(d) (0 at d == 0), Huber clamp(d, -delta, delta), SmoothL1
+ * clamp(d, -beta, beta), MSE d.  gscale is a device scalar. */
 int tribe_elem_loss_bwd(const float* pred, const float* truth, int64_t n, int32_t kind, float param, int32_t reduction,
                         const float* gscale, float* dpred, void* stream);
 /* adaptive average pool backward: dx[r, t] = sum_{i: t in window i} dy[r, i] / |window i| */

@@ -10,7 +10,8 @@ input element read once, each output element written once), GB/s and the fractio
 (MI355X_MICROARCH.md; ~6.3 TB/s is what a streaming kernel reaches in practice).  Run it under
 `rocprofv3 --kernel-trace --stats` for the per-kernel durations committed under profiles/.  The Pearson statistics run the
 shared kernel pair of csrc/bvt_stats.h (bvt_stats_rows_kernel<PearsonAcc>); the committed profiles list it under its
-earlier name, pearson_stats_rows_kernel (the same ISA)."""
+earlier name, pearson_stats_rows_kernel (the same ISA).  The MSE loss is the (MSE, mean) instance of csrc/robust_loss.hip's
+element-wise family; the committed profiles show the separate kernels it ran on before."""
 import json
 import sys
 from pathlib import Path
@@ -64,8 +65,8 @@ def pearson_bwd():
 
 
 cases = {
-    "mse_fwd (mse_partial_kernel)": (lambda: ops.mse(pred, true), 8 * n),
-    "mse_bwd (mse_bwd_kernel)": (mse_bwd, 12 * n),
+    "mse_fwd (elem_loss_partial_kernel<MSE>)": (lambda: ops.elem_loss(pred, true, "mse"), 8 * n),
+    "mse_bwd (elem_loss_bwd_kernel<MSE>)": (mse_bwd, 12 * n),
     "pearson_stats_update, one group (bvt_stats_rows_kernel<PearsonAcc>)": (lambda: ops.pearson_stats_update(stats1, pred, true), 8 * n),
     "pearson_stats_update, grouped by subject": (lambda: ops.pearson_stats_update(stats4, pred, true, subj), 8 * n),
     "pearson_loss_fwd (stats + final)": (lambda: ops.pearson_loss(pred, true), 8 * n),
@@ -83,7 +84,7 @@ r_ref = ((x - x.mean(0)) * (y - y.mean(0))).sum(0) / ((x - x.mean(0)).norm(dim=0
 st = torch.zeros(1, V, 6, dtype=torch.float64, device=dev)
 ops.pearson_stats_update(st, pred, true)
 out["max_abs_r_error_vs_f64"] = float((ops.pearson_from_stats(st)[0].double() - r_ref).abs().max())
-out["mse_rel_error_vs_f64"] = float(abs(ops.mse(pred, true).double() - ((x - y) ** 2).mean()) / ((x - y) ** 2).mean())
+out["mse_rel_error_vs_f64"] = float(abs(ops.elem_loss(pred, true, "mse").double() - ((x - y) ** 2).mean()) / ((x - y) ** 2).mean())
 print("max |r - r_f64| =", out["max_abs_r_error_vs_f64"], " mse rel err =", out["mse_rel_error_vs_f64"])
 if len(sys.argv) > 2:
     Path(sys.argv[2]).write_text(json.dumps(out, indent=1))

@@ -1,4 +1,4 @@
-"""The element-wise loss family (L1 / SmoothL1 / Huber / MSE 'sum': csrc/robust_loss.hip) against the path it replaces and against the
+"""The element-wise loss family (L1 / SmoothL1 / Huber / MSE: csrc/robust_loss.hip) against the path it replaces and against the
 HBM roofline.
 
 GPU box:  python scripts/robust_loss_bench.py [out.json]
@@ -7,9 +7,9 @@ Per kind, at [16, 1000, 100] (the reference's batch; 6.4 MB per tensor, launch-b
 per tensor, HBM-bound), forward + backward to a [B, V, T'] leaf of
   * the new path: the HIP loss's forward_bvt on the pair in place (partial sums, final sum, backward: three launches), and
   * the parent's path: the stock torch.nn loss on the two permuted, reshaped '(b t) d' copies, autograd back to the leaf.
-At [64, 1000, 1024] the forward and the backward entry points are also timed alone, next to tribe_mse_fwd / tribe_mse_bwd (the same
-streams with fewer VALU ops).  The MSE pair is measured twice per round: the gap between its two figures is the spread below which a
-difference means nothing on a shared machine.
+At [64, 1000, 1024] the forward and the backward entry points are also timed alone, next to tribe_mse_fwd / tribe_mse_bwd (the family's
+(MSE, mean) instance under its own names).  That pair is measured twice per round: the gap between its two figures is the spread
+below which a difference means nothing on a shared machine.
 
 Every variant of one shape is timed in turn within a round (alternated), ROUNDS rounds; the table shows the median over rounds of
 the per-call HIP-event time.  ALGORITHMIC bytes: each input element read once (forward 8 n, backward 8 n) and each gradient element
@@ -108,6 +108,12 @@ for (B, V, T), reps in SHAPES.items():
     if B * T >= 64 * 1024:
         p, t = pred.detach(), true
 
+        ws = torch.empty(lib().tribe_mse_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        loss = torch.empty((), device=dev)
+
+        def mse_fwd():
+            check(lib().tribe_mse_fwd(p.data_ptr(), t.data_ptr(), n, loss.data_ptr(), ws.data_ptr(), ws.numel(), stream), "tribe_mse_fwd")
+
         def mse_bwd():
             check(lib().tribe_mse_bwd(p.data_ptr(), t.data_ptr(), n, one.data_ptr(), dpred.data_ptr(), stream), "tribe_mse_bwd")
 
@@ -116,11 +122,11 @@ for (B, V, T), reps in SHAPES.items():
                                             one.data_ptr(), dpred.data_ptr(), stream), "tribe_elem_loss_bwd")
 
         # the MSE pair twice, around the new kernels: the gap between its two figures is the spread
-        kernels = {"mse_fwd (first)": lambda: ops.mse(p, t), "mse_bwd (first)": mse_bwd}
+        kernels = {"mse_fwd (first)": mse_fwd, "mse_bwd (first)": mse_bwd}
         for name, (_, kind, param, reduction) in KINDS.items():
             kernels[f"{name} fwd"] = lambda a=(kind, param, reduction): ops.elem_loss(p, t, *a)
             kernels[f"{name} bwd"] = lambda a=(kind, param, reduction): elem_bwd(*a)
-        kernels["mse_fwd (second)"] = lambda: ops.mse(p, t)
+        kernels["mse_fwd (second)"] = mse_fwd
         kernels["mse_bwd (second)"] = mse_bwd
         shape_out["entry_points"] = {}
         print("  entry points alone:")

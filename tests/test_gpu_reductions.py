@@ -337,17 +337,33 @@ def test_lse_rows_and_infonce_dlogits(N):
 
 
 # ------------------------------------------------------------------------------------------------
-# MSE forward (2048-workgroup capped grid, 4-deep float4 loop, float4 remainder, scalar tail for n % 4) and backward (4096-workgroup
-# grid, 2-deep loop); the last n runs the forward's unrolled loop three times over (4 x 4 x 2048 x 256 floats per trip)
+# tribe_mse_fwd / tribe_mse_bwd, the (MSE, mean) instance of csrc/robust_loss.hip's element-wise family: forward (2048-workgroup
+# capped grid, 4-deep float4 loop, float4 remainder, scalar tail for n % 4) and backward (4096-workgroup grid, 2-deep loop); the last
+# n runs the forward's unrolled loop three times over (4 x 4 x 2048 x 256 floats per trip)
 # ------------------------------------------------------------------------------------------------
+def _mse_fwd(pd, td, n):
+    """tribe_mse_fwd's return code and result on a workspace of tribe_mse_workspace_bytes(n)."""
+    from tribe_hip._lib import lib
+
+    ws = torch.empty(lib().tribe_mse_workspace_bytes(n), dtype=torch.uint8, device="cuda")
+    out = torch.full((), float("nan"), device="cuda")
+    rc = lib().tribe_mse_fwd(pd.data_ptr(), td.data_ptr(), n, out.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    return rc, out
+
+
 @pytest.mark.parametrize("n", [1, 3, 4, 5, 4097, 16_500, 64 * 1000 * 100, 3 * (4 * 4 * 2048 * 256) + 4 * 300_001 + 3])
 def test_mse_fwd_bwd(ops, n):
+    from tribe_hip._lib import check, lib
+
     g = torch.Generator().manual_seed(n % 100_003)
     pred = torch.randn(n, generator=g)
     true = torch.randn(n, generator=g).mul_(0.8).add_(pred, alpha=0.5)
     true[3::7] = pred[3::7]                                               # exact zeros of the gradient
     pd, td = pred.cuda(), true.cuda()
-    got = float(ops.mse(pd, td))
+    assert lib().tribe_mse_workspace_bytes(n) == lib().tribe_elem_loss_workspace_bytes(n)
+    rc, out = _mse_fwd(pd, td, n)
+    check(rc, "tribe_mse_fwd")
+    got = float(out)
     p64 = pred.double().requires_grad_()
     loss = (p64 - true.double()).pow(2).mean()
     # f32 squares summed in f32 chains of <= 16 terms, then in f64: 1e-5 relative
@@ -358,6 +374,21 @@ def test_mse_fwd_bwd(ops, n):
     gsd = torch.tensor([gs], device="cuda")
     _call("tribe_mse_bwd", pd.data_ptr(), td.data_ptr(), n, gsd.data_ptr(), dp.data_ptr())
     torch.testing.assert_close(dp.cpu().double(), grad, rtol=1e-4, atol=0)
+    if n in (5, 4097, 16_500):
+        # the partly filled workgroup, the unrolled loop plus tail, the remainder loop: the wrappers run the family's kernels with the
+        # family's (mse, mean) plan, so a single differing bit means a wrapper passes another factor
+        same = ops.elem_loss(pd, td, "mse", 0.0, "mean")
+        assert torch.equal(out.view(torch.int32), same.view(torch.int32)), f"mse n={n}: {got} vs elem_loss {float(same)}"
+        dq = torch.full((n,), float("nan"), device="cuda")
+        _call("tribe_elem_loss_bwd", pd.data_ptr(), td.data_ptr(), n, ops.ELEM_LOSS_KINDS["mse"], 0.0, ops.ELEM_LOSS_REDUCTIONS["mean"],
+              gsd.data_ptr(), dq.data_ptr())
+        assert torch.equal(dp.view(torch.int32), dq.view(torch.int32)), f"mse n={n}: tribe_mse_bwd and tribe_elem_loss_bwd differ in bits"
+    if n == 4097:
+        # the entry point's own contract: 16-byte aligned inputs (the family's entry point takes the scalar form there)
+        buf = torch.zeros(n + 1, device="cuda")
+        assert buf.data_ptr() % 16 == 0
+        with pytest.raises(ValueError, match="tribe_mse_fwd: inputs must be 16-byte aligned"):
+            check(_mse_fwd(buf[1:], td, n)[0], "tribe_mse_fwd")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ Bounds (u = 2^-24, one f32 rounding):
     a sum of non-negative terms, so relative to the result), the chains in f64, the result rounded once to f32: <= ~21 u = 1.3e-6.
     The bound is the project's standing 1e-5 relative for "f32 terms in f32 chains of <= 16, then f64": it is ~8 x that worst case and
     far below what a wrong branch, a wrong 1 / n or a dropped 1 / beta leaves.
-  * backward: d = p - t (u), the clamp is exact, times k = gs * fl(common factor) (2 u) and one product (u): 4 u relative per element;
+  * backward: d = p - t (u), the clamp is exact, times k = gs * num / den (2 u, num / den the factor common to all elements) and one product (u): 4 u relative per element;
     rtol 1e-4, atol 0, the existing loss-gradient bound.  atol = 0 makes an exact zero of the reference an exact zero here.
     An element within u |d| of the clamp point may take the other branch than f64 does: there both branches agree to u as well.
 """

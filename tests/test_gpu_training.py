@@ -76,7 +76,7 @@ def test_autograd_blocks_vs_torch():
     torch.testing.assert_close(xg.grad.cpu(), xt.grad, rtol=1e-5, atol=1e-6)
     p, t = torch.randn(4, 6, 9, generator=g), torch.randn(4, 6, 9, generator=g)
     pt = p.clone().requires_grad_(); (((pt - t) ** 2).mean() * 3.0).backward()
-    pg = p.to(dev).requires_grad_(); (ag.MSE.apply(pg, t.to(dev)) * 3.0).backward()
+    pg = p.to(dev).requires_grad_(); (ag.ElemLoss.apply(pg, t.to(dev), "mse", 0.0, "mean") * 3.0).backward()
     torch.testing.assert_close(pg.grad.cpu(), pt.grad, rtol=1e-5, atol=1e-7)
 
 

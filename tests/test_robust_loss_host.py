@@ -1,4 +1,4 @@
-"""CPU (no GPU): the host side of the element-wise loss family (L1 / SmoothL1 / Huber, MSE 'sum'): the classes and their argument
+"""CPU (no GPU): the host side of the element-wise loss family (L1 / SmoothL1 / Huber / MSE): the classes and their argument
 checks, `hip_loss_for`'s mapping from stock torch modules, the step's routing decision, and the C ABI declarations.  No kernel runs."""
 
 import re
@@ -73,7 +73,7 @@ def test_constructors_refuse_what_torch_refuses_at_call_time():
             cls(reduction="median")
 
 
-@pytest.mark.parametrize("loss", [L1Loss(), SmoothL1Loss(), HuberLoss(), MSELoss(reduction="sum")])
+@pytest.mark.parametrize("loss", [L1Loss(), SmoothL1Loss(), HuberLoss(), MSELoss(), MSELoss(reduction="sum")])
 def test_no_cpu_fallback(loss):
     from tribe_hip._lib import TribeHipError
 
