@@ -58,6 +58,26 @@ __device__ __forceinline__ double onepass_centred_ss(double s1, double s2, doubl
   const double v = s2 - s1 * s1 / n;
   return v > n * __DBL_EPSILON__ * s2 ? v : 0.0;
 }
+// ---- f32 -> e4m3 (OCP e4m3fn), four values to four bytes: saturating, round to nearest even, NaN passed through ----------------
+// The clamp keeps v_cvt_pk_fp8_f32 (which turns whatever rounds past 448 into NaN) saturating.  It is ONE ordered compare per value,
+// which a NaN fails: a NaN reaches the conversion and leaves as the NaN code, never as a finite +-448.  The clamp gives the MAGNITUDE
+// 448 only; the sign of every code comes from pack_e4m3x4 below.
+__device__ __forceinline__ float clamp_e4m3_magnitude(float f) {
+  return fabsf(f) > 448.f ? 448.f : f;
+}
+// The conversion gives every NaN the code 0xFF whatever its sign (measured: tests/test_gpu_fp8_bounds.py), while every other code
+// carries the sign of its input, zeros included.  So the four sign bits are taken from the inputs -- two byte gathers (v_perm_b32: the
+// top byte of each float into its code's place) and one bit select, no compare -- and only the NaN bytes (and the clamped ones, whose
+// sign the clamp dropped) change: +NaN -> 0x7F, -NaN -> 0xFF, the codes of torch's float8_e4m3fn cast.
+__device__ __forceinline__ int pack_e4m3x4(float a, float b, float c, float d) {
+  int pk = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3_magnitude(a), clamp_e4m3_magnitude(b), 0, false);
+  pk = __builtin_amdgcn_cvt_pk_fp8_f32(clamp_e4m3_magnitude(c), clamp_e4m3_magnitude(d), pk, true);
+  // v_perm_b32 selects from {src0, src1}: 0..3 = bytes of src1, 4..7 = bytes of src0, 0x0c = zero
+  const unsigned int top = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x0c0c0703u) |
+                           __builtin_amdgcn_perm(__float_as_uint(d), __float_as_uint(c), 0x07030c0cu);
+  return (int)((top & 0x80808080u) | ((unsigned int)pk & 0x7F7F7F7Fu));
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));

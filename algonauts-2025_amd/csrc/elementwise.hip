@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256) void rotary_kernel(unsigned short* __restrict_
 
 // ---------------------------------------------------------------------------------
 // RMSNorm / LayerNorm: one wave per row (f32 in, f32 statistics), bf16 or f32 out; OUT_BF16 == 2: e4m3 bytes of the
-// bf16-rounded result times q_inv_scale, saturating (= the bf16 norm followed by tribe_quantize_fp8_fwd, bit for bit, in one pass)
+// bf16-rounded result times q_inv_scale, saturating, NaN passed through (= the bf16 norm followed by tribe_quantize_fp8_fwd, bit for bit, in one pass)
 // ---------------------------------------------------------------------------------
 template <int OUT_BF16, int LAYERNORM>
 __global__ __launch_bounds__(256) void rowstat_norm_kernel(const float* __restrict__ x, int64_t rows, int64_t dim,
@@ -264,10 +264,8 @@ __global__ __launch_bounds__(256) void rowstat_norm_kernel(const float* __restri
     if (OUT_BF16 == 2) {
       float q[4] = {o0, o1, o2, o3};
 #pragma unroll
-      for (int j = 0; j < 4; ++j) q[j] = fminf(fmaxf(bf16_to_f32(f32_to_bf16(q[j])) * q_inv_scale, -448.f), 448.f);
-      int pk = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
-      pk = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], pk, true);
-      ((int*)((unsigned char*)y + row * dim))[i] = pk;
+      for (int j = 0; j < 4; ++j) q[j] = bf16_to_f32(f32_to_bf16(q[j])) * q_inv_scale;
+      ((int*)((unsigned char*)y + row * dim))[i] = pack_e4m3x4(q[0], q[1], q[2], q[3]);
     } else if (OUT_BF16) {
       u16x4_t o;
       o[0] = f32_to_bf16(o0); o[1] = f32_to_bf16(o1); o[2] = f32_to_bf16(o2); o[3] = f32_to_bf16(o3);
@@ -334,10 +332,8 @@ __global__ __launch_bounds__(256) void rowstat_norm_reg_kernel(const float* __re
     if (OUT_BF16 == 2) {
       float q[4] = {o0, o1, o2, o3};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) q[k] = fminf(fmaxf(bf16_to_f32(f32_to_bf16(q[k])) * q_inv_scale, -448.f), 448.f);
-      int pk = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
-      pk = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], pk, true);
-      ((int*)((unsigned char*)y + row * dim))[i] = pk;
+      for (int k = 0; k < 4; ++k) q[k] = bf16_to_f32(f32_to_bf16(q[k])) * q_inv_scale;
+      ((int*)((unsigned char*)y + row * dim))[i] = pack_e4m3x4(q[0], q[1], q[2], q[3]);
     } else if (OUT_BF16) {
       u16x4_t o;
       o[0] = f32_to_bf16(o0); o[1] = f32_to_bf16(o1); o[2] = f32_to_bf16(o2); o[3] = f32_to_bf16(o3);

@@ -197,6 +197,8 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_nt_256x256x128(const tribe_ge
 
 // ---- quantisation: out[m, k] = e4m3(clamp(x[m, k] * inv_scale, +-448)), columns K..K_pad zero ------------------------
 // v_cvt_pk_fp8_f32 rounds to nearest even into OCP e4m3fn on gfx950; the clamp makes it saturating (448 = max finite).
+// NaN is passed through (pack_e4m3x4, common.h): the clamp is one ordered compare that a NaN fails, so it leaves as the NaN code with
+// its sign (+NaN 0x7F, -NaN 0xFF) -- never as a finite +-448.
 template <typename T>
 __global__ __launch_bounds__(256) void quantize_fp8_kernel(const T* __restrict__ x, int64_t M, int64_t K, int64_t ld, float inv_scale,
                                                            unsigned char* __restrict__ out, int64_t K_pad) {
@@ -212,27 +214,31 @@ __global__ __launch_bounds__(256) void quantize_fp8_kernel(const T* __restrict__
         if (sizeof(T) == 2) f = bf16_to_f32(((const unsigned short*)x)[m * ld + k + j]);
         else f = ((const float*)x)[m * ld + k + j];
       }
-      f *= inv_scale;
-      v[j] = fminf(fmaxf(f, -448.f), 448.f);
+      v[j] = f * inv_scale;
     }
-    int pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
-    pk = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], pk, true);
-    *(int*)(out + m * K_pad + k) = pk;
+    *(int*)(out + m * K_pad + k) = pack_e4m3x4(v[0], v[1], v[2], v[3]);
   }
 }
 
 // ---- amax over a tensor (calibration of per-tensor scales): atomic max on the bit pattern of |x| ---------------------
+// The running maximum is taken on the bit patterns as well (unsigned): |x| >= 0 orders like its pattern, inf is above every
+// finite value and a NaN above inf, so a NaN anywhere in the tensor makes the result NaN (fmaxf would drop it).
 template <typename T>
 __global__ __launch_bounds__(256) void absmax_kernel(const T* __restrict__ x, int64_t M, int64_t K, int64_t ld, unsigned int* __restrict__ out) {
-  float best = 0.f;
+  unsigned int best = 0u;
   const int64_t total = M * K;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     const int64_t m = idx / K, k = idx - m * K;
     const float f = sizeof(T) == 2 ? bf16_to_f32(((const unsigned short*)x)[m * ld + k]) : ((const float*)x)[m * ld + k];
-    best = fmaxf(best, fabsf(f));
+    const unsigned int u = __float_as_uint(f) & 0x7FFFFFFFu;
+    best = u > best ? u : best;
   }
-  best = wave_max(best);
-  if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(best));   // non-negative floats order like their bit patterns
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned int o = (unsigned int)__shfl_xor((int)best, off, 64);
+    best = o > best ? o : best;
+  }
+  if ((threadIdx.x & 63) == 0) atomicMax(out, best);   // non-negative floats order like their bit patterns
 }
 
 }  // namespace

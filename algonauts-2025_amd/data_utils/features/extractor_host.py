@@ -5,6 +5,7 @@ launch on the current stream).  A subclass supplies its weight-name table, its d
 from __future__ import annotations
 
 import ctypes as C
+import math
 import typing as tp
 
 import torch
@@ -56,14 +57,18 @@ class ExtractorHost:
         amax = torch.zeros(max(self.depth, 1), 4, dtype=torch.float32, device=self.device)
         self._calibrate(calibration, amax)
         table = amax.cpu()                                    # one-time sync: the scales become launch constants
-        if not bool((table[: self.depth] > 0).all()):
-            raise ValueError("fp8 calibration saw an all-zero GEMM input")
+        seen = table[: self.depth]
+        if not bool((torch.isfinite(seen) & (seen > 0)).all()):   # tribe_absmax_fwd reports a NaN / inf anywhere in a tensor as NaN / inf
+            raise ValueError(f"fp8 calibration saw an all-zero or non-finite (NaN / inf) GEMM input: amax per layer {seen.tolist()}")
         layers = (self.FP8_LAYER * max(self.depth, 1))()
         self.fp8_packs = []
         for i in range(self.depth):
             q = []
             for j, (field, w) in enumerate(zip(self.FP8_FIELDS, getattr(self, self.FP8_SOURCE)[i])):
-                w_scale = float(ops.absmax(w)) / ops.FP8_MAX
+                w_amax = float(ops.absmax(w))
+                if not (math.isfinite(w_amax) and w_amax > 0):
+                    raise ValueError(f"fp8: layer {i} weight {field} has amax {w_amax}: an all-zero or non-finite tensor has no e4m3 scale")
+                w_scale = w_amax / ops.FP8_MAX
                 q.append(ops.quantize_fp8(w, w_scale, K_pad=w.shape[1]))
                 setattr(layers[i], field, q[-1].data_ptr())
                 layers[i].w_scale[j] = w_scale

@@ -735,7 +735,8 @@ int tribe_corr_matrix_fwd(const float* x, int64_t N, int64_t K, double* corr, vo
  * per-tensor quantisation.  v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales, f32 accumulation. */
 int tribe_gemm_fp8(const tribe_gemm_desc* d, void* stream);
 /* out[m, k] = e4m3(clamp(x[m, k] * inv_scale, -448, 448)) (round to nearest even), x f32 | bf16 [M, K] with row stride ld,
- * out [M, K_pad] bytes, columns K..K_pad zero; K_pad a multiple of 16. */
+ * out [M, K_pad] bytes, columns K..K_pad zero; K_pad a multiple of 16.  Saturating: +-inf and everything past 448 give +-448.
+ * Zeros keep their sign.  A NaN is passed through as the NaN code with its sign (+NaN 0x7F, -NaN 0xFF), never as a finite value. */
 int tribe_quantize_fp8_fwd(const void* x, int32_t x_dtype, int64_t M, int64_t K, int64_t ld, float inv_scale, uint8_t* out,
                            int64_t K_pad, void* stream);
 /* The pre-norm of an extractor layer fused with the quantisation of the Linear input that follows it (transformers' LlamaRMSNorm /
@@ -744,7 +745,8 @@ int tribe_quantize_fp8_fwd(const void* x, int32_t x_dtype, int64_t M, int64_t K,
  * (f32 [rows, dim], dim % 16 == 0; y8 [rows, dim] bytes). */
 int tribe_norm_quantize_fp8_fwd(const float* x, int64_t rows, int64_t dim, const float* w, const float* b, int32_t layernorm, float eps,
                                 float inv_scale, uint8_t* y8, void* stream);
-/* out[0] = max(out[0] if accumulate else 0, max |x|)  (device float; calibration of the per-tensor scales) */
+/* out[0] = max(out[0] if accumulate else 0, max |x|)  (device float; calibration of the per-tensor scales).  A NaN anywhere in x, or
+ * already in out[0] when accumulating, gives NaN (it orders above inf), so that poisoned activations cannot yield a usable scale. */
 int tribe_absmax_fwd(const void* x, int32_t x_dtype, int64_t M, int64_t K, int64_t ld, float* out, int32_t accumulate, void* stream);
 
 /* ---- optimiser step of pl_module.training_step's loop (grids/defaults.py:126-133: torch.optim.Adam, lr 1e-4, wd 0) ----

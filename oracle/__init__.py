@@ -22,6 +22,11 @@ Contents
                    modes, the conv module, pools, window means, piece and CSR
                    sums, and a bf16 rounding helper on bit patterns.
 
+* `fp8_ref`     -- the OCP e4m3 decode table and round-to-nearest-even encoder
+                   from the format definition (numpy only), the float64 GEMM
+                   epilogue in the kernel's operator order, and the j / 8
+                   operands whose f32 sums are exact in any order.
+
 Pinning status (see DESIGN.md "Oracle")
 ---------------------------------------
 * Everything that lives in the reference's own files (SubjectLayers,

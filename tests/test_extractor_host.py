@@ -113,3 +113,48 @@ def test_feature_plugin_surface_matches_the_reference_fields():
         with pytest.raises(RuntimeError, match="no CPU path"):
             Wav2VecBert().prepare([s])
     assert Wav2VecBert()._item_uid(s) == "a.wav_0.00_3.00" and LLAMA3p2()._item_uid(Word(start=0, text="a", context="b a")) == "a_b a"
+
+
+def test_enable_fp8_refuses_a_zero_or_non_finite_amax(monkeypatch):
+    """ExtractorHost.enable_fp8 builds the e4m3 scales from amax values (calibration inputs, then weights): a zero has no scale, and
+    tribe_absmax_fwd reports a NaN / inf anywhere in a tensor as NaN / inf -- each must stop the switch to fp8, not become a scale."""
+    import ctypes as C
+
+    import pytest
+
+    from data_utils.features import extractor_host
+    from tribe_hip import _lib
+
+    class Host(extractor_host.ExtractorHost):
+        FP8_LAYER, FP8_FIELDS, FP8_WIDTHS_ERROR = _lib.LlamaFp8Layer, ("w_qkv", "w_o", "w_gate_up", "w_down"), "widths"
+        depth = 2
+
+        def __init__(self, seen):
+            super().__init__({}, {}, "cpu")
+            self.fp8_widths, self.seen = (128, 256), seen
+            self.packs = [[torch.full((4, 128), float(1 + i + j)) for j in range(4)] for i in range(2)]
+
+        def _calibrate(self, calibration, amax):
+            amax.copy_(self.seen)
+
+    weight_amax = {}
+    monkeypatch.setattr(extractor_host.ops, "absmax", lambda w: torch.tensor([weight_amax.get(float(w[0, 0]), float(w.abs().max()))]))
+    monkeypatch.setattr(extractor_host.ops, "quantize_fp8", lambda w, scale, K_pad=None: torch.zeros(w.shape[0], K_pad, dtype=torch.uint8))
+    good = torch.tensor([[1.0, 2.0, 3.0, 4.0], [0.5, 6.0, 7.0, 448.0]])
+    host = Host(good)
+    assert torch.equal(host.enable_fp8(torch.zeros(1)), good) and host.fp8_layers is not None
+    assert host.fp8_layers[1].in_scale[3] == 1.0 and host.fp8_layers[0].w_scale[1] == np.float32(2.0 / 448.0)
+    for bad in (0.0, float("nan"), float("inf"), -float("inf"), -1.0):
+        seen = good.clone()
+        seen[1, 2] = bad
+        host = Host(seen)
+        with pytest.raises(ValueError, match="calibration"):
+            host.enable_fp8(torch.zeros(1))
+        assert host.fp8_layers is None
+    for bad in (0.0, float("nan"), float("inf")):
+        weight_amax.clear()
+        weight_amax[3.0] = bad          # layer 0 field 2 and layer 1 field 1 are filled with 3.0
+        host = Host(good)
+        with pytest.raises(ValueError, match="weight"):
+            host.enable_fp8(torch.zeros(1))
+        assert host.fp8_layers is None
