@@ -37,16 +37,20 @@ __device__ __forceinline__ void tile_coords(int bid, int tiles_m, int tiles_n, i
 
 // GELU(v) = v * Phi(v) for TWO values at once, used where the result is rounded to bf16 anyway.  No transcendental:
 // Phi(v) - 0.5 = v * Q(v^2) on |v| <= 4.4 (degree-8 minimax-style fit, |Phi error| <= 1.9e-5), argument clamped beyond
-// (Phi -> 0 / 1 within 1e-5).  |GELU error| <= 8.3e-5 absolute over all v (checked in f32 on a 2M-point grid) -- two
-// orders below the bf16 rounding of the values it feeds.  Every step is a packed-f32 operation (v_pk_mul_f32 /
+// (Phi -> 0 / 1 within 1e-5).  The LOWER clamp sits on the fit's zero just inside -4.4 (GELU_POLY2_LO: Phi evaluates to 6.6e-9 there),
+// so that v * Phi goes to 0 below it as GELU does: clamped at -4.4 itself the fit gives Phi = -4.1e-6, and the result GREW with |v|
+// -- +4e-4 at v = -100, found by tests/test_gpu_gemm_bounds.py.  |GELU error| <= 8.3e-5 absolute for -8192 <= v <= 15 (held there by that test), and
+// <= 5.5e-6 |v| above, where Phi stays at Phi(4.4) (checked in f32 on a 2M-point grid) -- two orders below the bf16 rounding of
+// the values it feeds.  Every step is a packed-f32 operation (v_pk_mul_f32 /
 // v_pk_fma_f32: two values per issue): 12 issues per pair against ~44 for two erfc-polynomial evaluations with
 // v_exp_f32 + v_rcp_f32 at quarter rate (the round-1 epilogue): FF1 3.93 -> 3.80 ms once the epilogue stopped waiting
 // on memory.
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+constexpr float GELU_POLY2_LO = -4.39382219f;   // 0xc08c9a31: the f32 at which the fit's Phi is closest to 0
 __device__ __forceinline__ f32x2_t gelu_poly2(f32x2_t v) {
   f32x2_t c;
-  c.x = __builtin_amdgcn_fmed3f(v.x, -4.4f, 4.4f);
-  c.y = __builtin_amdgcn_fmed3f(v.y, -4.4f, 4.4f);
+  c.x = __builtin_amdgcn_fmed3f(v.x, GELU_POLY2_LO, 4.4f);
+  c.y = __builtin_amdgcn_fmed3f(v.y, GELU_POLY2_LO, 4.4f);
   const f32x2_t t = c * c;
   f32x2_t q = 4.4347532590638394e-11f;
   q = q * t + -4.493755145773548e-09f;

@@ -27,6 +27,13 @@ Contents
                    epilogue in the kernel's operator order, and the j / 8
                    operands whose f32 sums are exact in any order.
 
+* `gemm_ref`    -- the bf16 GEMM's whole descriptor in float64 (the fp8 epilogue
+                   plus row_scale, EXP2, MUL_AUX, GELU_BWD, the stored
+                   pre-activation, transposed operands, batches, gather1), the
+                   integer operands whose f32 sums are exact in any order and
+                   under any split of K, and replays of the launcher's stream-K
+                   and split-K plans with the case table of the GPU test.
+
 Pinning status (see DESIGN.md "Oracle")
 ---------------------------------------
 * Everything that lives in the reference's own files (SubjectLayers,
