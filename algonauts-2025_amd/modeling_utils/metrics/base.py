@@ -89,7 +89,8 @@ class OnlinePearsonCorr(MultidimPearsonCorrCoef):
         super().reset()
 
 
-# metrics/rank_corr.py adds "MultidimSpearmanCorrCoef" (it imports this module, so the entry is made there)
+# metrics/rank_corr.py adds "MultidimSpearmanCorrCoef" and metrics/bootstrap.py "BootstrapPearsonCorrCoef" (they import this module, so
+# the entries are made there)
 _BASE_METRICS = {"MultidimPearsonCorrCoef": MultidimPearsonCorrCoef, "OnlinePearsonCorr": OnlinePearsonCorr}
 
 
@@ -144,6 +145,14 @@ class GroupedMetric(nn.Module):
         r = self._state.per_output()  # [G, V]
         means = r.mean(dim=1).tolist()
         return {gid: means[self._index[gid]] for gid in self._ids}
+
+    def intervals(self) -> dict[str, tp.Any]:
+        """{group_id: result} of a sub-metric that resamples (metrics/bootstrap.py): every group from its own blocks."""
+        if not hasattr(self.base_metric_cls, "intervals"):
+            raise TypeError(f"{self.base_metric_cls.__name__} has no intervals()")
+        if self._state is None or not self._ids:
+            return {}
+        return {gid: self._state.intervals(group=self._index[gid]) for gid in self._ids}
 
     def sync(self, group: tp.Any = None) -> None:
         if self._state is not None:

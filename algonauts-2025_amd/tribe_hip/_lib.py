@@ -292,6 +292,9 @@ SIGNATURES = {
     "tribe_spearman_workspace_bytes": (sz, [i64, i64, i64]),
     "tribe_spearman_default_chunk": (i64, []),
     "tribe_spearman_max_samples": (i64, []),
+    "tribe_bootstrap_counts": (C.c_int, [C.c_uint64, i64, i64, vp, vp]),
+    "tribe_bootstrap_pearson": (C.c_int, [vp, i64, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
+    "tribe_bootstrap_summary": (C.c_int, [vp, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp]),
     "tribe_fbank_workspace_bytes": (sz, [C.POINTER(i64), i32]),
     "tribe_fbank_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, vp, vp, vp, i64, C.POINTER(i32), vp, sz, vp]),
     "tribe_resample_frac_fwd": (C.c_int, [C.POINTER(vp), C.POINTER(i64), i32, i32, i32, i32, i32, vp, C.POINTER(vp), C.POINTER(i64), vp]),

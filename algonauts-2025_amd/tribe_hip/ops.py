@@ -927,6 +927,101 @@ def rank_columns(x: torch.Tensor, chunk: int = 0) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------
+# block bootstrap of the per-parcel Pearson r (csrc/bootstrap.hip)
+# --------------------------------------------------------------------------------------
+BOOTSTRAP_MAX_BLOCKS = 32768       # n_sel: one replicate's int32 histogram lives in LDS (128 KiB)
+BOOTSTRAP_MAX_REPLICATES = 16384   # one column of replicates is sorted in LDS (64 KiB of keys)
+
+
+def bootstrap_counts(seed: int, n_boot: int, n_sel: int, device: torch.device | str) -> torch.Tensor:
+    """int32 [n_boot, n_sel]: how often replicate r draws each of n_sel blocks.  Draw k of replicate r is word k & 3 of Philox4x32-10
+    with counter (k >> 2, r, 0, 0) and key (seed & 0xffffffff, seed >> 32), mapped to the index (u * n_sel) >> 32.  The map is not
+    rejection-corrected: an index is over-represented by less than n_sel / 2^32 (< 8e-6 at the limit of 32768 blocks).  The draw
+    depends on (seed, r, k, n_sel) alone, so equal seeds resample two models identically."""
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+        raise ValueError(f"bootstrap_counts: seed must be an integer in [0, 2^64), got {seed!r}")
+    if not 1 <= n_boot <= BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"bootstrap_counts: n_boot = {n_boot} outside [1, {BOOTSTRAP_MAX_REPLICATES}]")
+    if not 1 <= n_sel <= BOOTSTRAP_MAX_BLOCKS:
+        raise ValueError(f"bootstrap_counts: n_sel = {n_sel} blocks outside [1, {BOOTSTRAP_MAX_BLOCKS}]")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.TribeHipError(f"bootstrap_counts: device {device}; the TRIBE hot path runs on the GPU only (no CPU fallback)")
+    counts = torch.empty(n_boot, n_sel, dtype=torch.int32, device=device)
+    check(lib().tribe_bootstrap_counts(seed, n_boot, n_sel, counts.data_ptr(), _stream()), "tribe_bootstrap_counts")
+    return counts
+
+
+def bootstrap_pearson(stats: torch.Tensor, blocks: torch.Tensor, counts: torch.Tensor | None
+                      ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """stats f64 [n_blocks, V, 6] (pearson_stats_update with one group per block), blocks int64 [n_sel] (the resampled blocks),
+    counts int32 [n_boot, n_sel] or None (the observed values alone) -> (observed f32 [V], replicates f32 [n_boot, V], mean_observed
+    f32 [], mean_replicates f32 [n_boot]).  Replicate r of parcel v is pearson_from_stats' rule on sum_j counts[r, j] *
+    stats[blocks[j], v] (f64, j ascending); `observed` takes every count as 1 through the same kernel.  The means are over parcels
+    (NaN when one parcel is NaN).  The four results are views of one [n_boot + 1, V + 1] table."""
+    _cuda(stats, torch.float64, "stats")
+    _cuda(blocks, torch.int64, "blocks")
+    if stats.ndim != 3 or stats.shape[2] != 6 or stats.shape[0] == 0 or stats.shape[1] == 0:
+        raise ValueError(f"bootstrap_pearson: stats must be a non-empty [n_blocks, V, 6], got {tuple(stats.shape)}")
+    n_blocks, V, _ = stats.shape
+    n_sel = blocks.numel()
+    if blocks.ndim != 1 or not 1 <= n_sel <= BOOTSTRAP_MAX_BLOCKS:
+        raise ValueError(f"bootstrap_pearson: blocks must be int64 [n_sel], 1 <= n_sel <= {BOOTSTRAP_MAX_BLOCKS}, got {tuple(blocks.shape)}")
+    n_boot = 0
+    if counts is not None:
+        _cuda(counts, torch.int32, "counts")
+        if counts.ndim != 2 or counts.shape[1] != n_sel or not 1 <= counts.shape[0] <= BOOTSTRAP_MAX_REPLICATES:
+            raise ValueError(f"bootstrap_pearson: counts must be [n_boot <= {BOOTSTRAP_MAX_REPLICATES}, {n_sel}], got {tuple(counts.shape)}")
+        n_boot = counts.shape[0]
+    table = torch.empty(n_boot + 1, V + 1, dtype=torch.float32, device=stats.device)
+    check(lib().tribe_bootstrap_pearson(stats.data_ptr(), n_blocks, V, blocks.data_ptr(), n_sel, _p(counts), n_boot, table.data_ptr(), V + 1,
+                                        table.data_ptr() + 4 * V, V + 1, _stream()), "tribe_bootstrap_pearson")
+    return table[n_boot, :V], table[:n_boot, :V], table[n_boot, V], table[:n_boot, V]
+
+
+@_functools.lru_cache(maxsize=16)
+def _quantile_tensor(qs: tuple[float, ...], device: torch.device) -> torch.Tensor:
+    return torch.tensor(qs, dtype=torch.float64, device=device)   # read by the kernel only: one upload per (quantiles, device)
+
+
+def bootstrap_summary(replicates: torch.Tensor, quantiles: tp.Sequence[float]
+                      ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Per column of replicates f32 [n, C] (rows may be strided, n <= 16384), over the column's m non-NaN values: (quantile values
+    f32 [n_q, C] by numpy's "linear" rule, std f32 [C] with ddof = 1 (NaN for m < 2), n_le int32 [C] = #{x <= 0}, n_ge int32 [C] =
+    #{x >= 0}, n_valid int32 [C] = m).  A column without a valid value has NaN quantiles."""
+    _cuda(replicates, torch.float32, "replicates", contiguous=False)
+    if replicates.ndim != 2 or replicates.shape[0] == 0 or replicates.shape[1] == 0:
+        raise ValueError(f"bootstrap_summary: expected a non-empty [n, C] table, got {tuple(replicates.shape)}")
+    n, Cn = replicates.shape
+    if n > BOOTSTRAP_MAX_REPLICATES:
+        raise ValueError(f"bootstrap_summary: {n} replicates exceed {BOOTSTRAP_MAX_REPLICATES}")
+    if Cn > 1 and replicates.stride(1) != 1 or replicates.stride(0) < Cn:
+        replicates = replicates.contiguous()
+    qs = [float(q) for q in quantiles]
+    if not qs or not all(0.0 <= q <= 1.0 for q in qs):
+        raise ValueError(f"bootstrap_summary: quantiles must be a non-empty sequence of values in [0, 1], got {quantiles!r}")
+    dev = replicates.device
+    q_dev = _quantile_tensor(tuple(qs), dev)
+    qv = torch.empty(len(qs), Cn, dtype=torch.float32, device=dev)
+    sd = torch.empty(Cn, dtype=torch.float32, device=dev)
+    cnt = torch.empty(3, Cn, dtype=torch.int32, device=dev)
+    check(lib().tribe_bootstrap_summary(replicates.data_ptr(), n, Cn, replicates.stride(0), q_dev.data_ptr(), len(qs), qv.data_ptr(),
+                                        sd.data_ptr(), cnt[0].data_ptr(), cnt[1].data_ptr(), cnt[2].data_ptr(), _stream()),
+          "tribe_bootstrap_summary")
+    return qv, sd, cnt[0], cnt[1], cnt[2]
+
+
+def bootstrap_p_values(n_le: torch.Tensor, n_ge: torch.Tensor, n_valid: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(p_le, p_ge, two-sided) f32 from bootstrap_summary's counts: p_le = (1 + #{x <= 0}) / (m + 1) (H0: the value is <= 0),
+    p_ge = (1 + #{x >= 0}) / (m + 1), two-sided = min(1, 2 min(p_le, p_ge)); f64 ratios rounded once; NaN for m = 0."""
+    m = n_valid.double()
+    p = (1.0 + torch.stack([n_le, n_ge]).double()) / (m + 1.0)
+    p = torch.cat([p, torch.clamp(2.0 * p.min(0, keepdim=True).values, max=1.0)])
+    p = torch.where(m > 0, p, float("nan")).float()
+    return p[0], p[1], p[2]
+
+
+# --------------------------------------------------------------------------------------
 # measurement hook: HIP events around every GEMM launch, summed per operator role
 # --------------------------------------------------------------------------------------
 def prof_begin(max_records: int = 4096) -> None:

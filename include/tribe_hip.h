@@ -551,6 +551,25 @@ int tribe_spearman_columns(const float* pred, const float* truth, int64_t ld, in
 size_t tribe_spearman_workspace_bytes(int64_t n, int64_t V, int64_t chunk);
 int64_t tribe_spearman_default_chunk(void);
 int64_t tribe_spearman_max_samples(void);
+/* Block bootstrap of the per-parcel Pearson r (modeling_utils/metrics/bootstrap.py: BootstrapPearsonCorrCoef), csrc/bootstrap.hip.
+ * counts: int32 [n_boot][n_sel], how often replicate r draws each of n_sel blocks.  Draw k of replicate r is word k & 3 of
+ *   Philox4x32-10 with counter (k >> 2, r, 0, 0) and key (seed & 0xffffffff, seed >> 32), mapped to (u * n_sel) >> 32 (64-bit
+ *   product, no rejection step: the bias is below n_sel / 2^32).  1 <= n_boot <= 16384, 1 <= n_sel <= 32768. */
+int tribe_bootstrap_counts(uint64_t seed, int64_t n_boot, int64_t n_sel, int32_t* counts, void* stream);
+/* stats: f64 [n_blocks][V][6] block statistics (the state of tribe_pearson_stats_update, one group per block); blocks: int64 [n_sel]
+ * (device), the blocks that are resampled, each in [0, n_blocks) (one outside makes every result NaN).  For r < n_boot and parcel v:
+ *   S = sum_j counts[r][j] * stats[blocks[j]][v][0..6), f64, j ascending;  r[r * ld + v] = tribe_pearson_from_stats' rule on S
+ * and row n_boot takes every count as 1 (the observed r): r is f32 [n_boot + 1][ld], ld >= V.  n_boot == 0 (counts may be NULL)
+ * gives the observed row alone.  mean[row * mean_stride] = the mean over v of the row's f32 results, summed in f64 in a fixed order
+ * and rounded once (NaN when a parcel is NaN).  No floating-point atomics: equal inputs give equal bits. */
+int tribe_bootstrap_pearson(const double* stats, int64_t n_blocks, int64_t V, const int64_t* blocks, int64_t n_sel,
+                            const int32_t* counts, int64_t n_boot, float* r, int64_t ld, float* mean, int64_t mean_stride, void* stream);
+/* Per column c of replicates f32 [n][ld] (c < C <= ld, 1 <= n <= 16384), over its m non-NaN values sorted ascending (s):
+ *   quantile_values[k * C + c] = s[i] + (h - i) (s[min(i + 1, m - 1)] - s[i]), h = (m - 1) quantiles[k], i = floor(h)  (numpy's "linear";
+ *     f64, rounded once; quantiles: f64 [n_q] on the device, each in [0, 1]; NaN for m = 0)
+ *   std[c] = sqrt(sum (s - mean)^2 / (m - 1)) (two passes, f64; NaN for m < 2);  n_le[c] = #{s <= 0}, n_ge[c] = #{s >= 0}, n_valid[c] = m. */
+int tribe_bootstrap_summary(const float* replicates, int64_t n, int64_t C, int64_t ld, const double* quantiles, int64_t n_q,
+                            float* quantile_values, float* std, int32_t* n_le, int32_t* n_ge, int32_t* n_valid, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Backward building blocks (pl_module.training_step: loss.backward() of the path).
