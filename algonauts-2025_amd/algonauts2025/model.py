@@ -20,10 +20,23 @@ Data flow of `forward` (every step a HIP launch through libtribe_hip.so, nothing
 fp32 master parameters live in torch; bf16 packed copies are cached per parameter version.
 In `.eval()` / no-grad mode this fused path runs and records no autograd graph; in `.train()` mode with grad enabled
 `forward` composes the same arithmetic from the autograd functions of modeling_utils/autograd.py (HIP forward AND backward).
+
+Dropout (extensions `ff_dropout`, `layer_dropout`, `projector_dropout`; all 0 by default) acts on that autograd training path only: the
+fused path applies none, train mode under `no_grad` included (the reference's modules would drop there).  Each training pass with an active
+`ff_dropout` or `projector_dropout` draws one key (modeling_utils.models.common.draw_dropout_key: torch's default CPU generator) right
+after its modality-dropout draw -- the prediction pass and the contrastive pass each draw their own -- and every mask of the pass is
+tribe_dropout_apply with that key and a site:
+    encoder feed-forward of layer i          (1 << 56) | i
+    projector of modality m, hidden block j  (2 << 56) | (m << 16) | j        (m: position in feature_dims;
+    contrastive head of m, hidden block j    (3 << 56) | (m << 16) | j         output dropout: j = MLP_OUT_BLOCK = 0xFFFF)
+`layer_dropout` follows x_transformers: per sub-layer (attention, then feed-forward, per depth) `random.random() < layer_dropout` skips
+norm, block and residual scaling; the draws use Python's `random` and are made only when layer_dropout > 0.  `last_dropout_key` and
+`last_layer_drops` keep the last pass's key and skip pattern.  With any of the three active the two passes never share latents.
 """
 
 from __future__ import annotations
 
+import random
 import typing as tp
 
 import numpy as np
@@ -33,9 +46,12 @@ from torch import nn
 
 from data_utils.dataloader import SegmentData
 from modeling_utils._pack import PackCache, f32c
-from modeling_utils.models.common import Mlp, MlpConfig, SubjectLayers
+from modeling_utils.models.common import Mlp, MlpConfig, SubjectLayers, draw_dropout_key
 from modeling_utils.models.transformer import TransformerEncoderConfig
 from tribe_hip import ops
+
+
+SITE_FF, SITE_PROJECTOR, SITE_HEAD = 1, 2, 3   # kinds of dropout site (module docstring); 0 = an Mlp used on its own
 
 
 class FmriEncoderConfig(pydantic.BaseModel):
@@ -66,6 +82,24 @@ class FmriEncoderConfig(pydantic.BaseModel):
     # hidden sizes of every modality projector and contrastive head (MlpConfig.hidden_sizes): Linear -> LayerNorm -> GELU per size in
     # front of the output Linear.  None = the reference's single Linear (model.py:61, 64)
     projector_hidden_sizes: list[int] | None = None
+    # dropout of the training path (module docstring): on the encoder's feed-forward hidden (0 <= p < 1), x_transformers' stochastic
+    # depth per sub-layer (0 <= p <= 1), and MlpConfig.dropout of the MLP projectors / contrastive heads (0 <= p < 1; needs
+    # projector_hidden_sizes).  The reference hard-codes all three as 0 (model.py:62, 109-111)
+    ff_dropout: float = 0.0
+    layer_dropout: float = 0.0
+    projector_dropout: float = 0.0
+
+    @pydantic.model_validator(mode="after")
+    def _check_dropout(self) -> "FmriEncoderConfig":
+        if not 0.0 <= self.ff_dropout < 1.0:
+            raise ValueError(f"ff_dropout must satisfy 0 <= p < 1, got {self.ff_dropout}")
+        if not 0.0 <= self.layer_dropout <= 1.0:
+            raise ValueError(f"layer_dropout must satisfy 0 <= p <= 1, got {self.layer_dropout}")
+        if not 0.0 <= self.projector_dropout < 1.0:
+            raise ValueError(f"projector_dropout must satisfy 0 <= p < 1, got {self.projector_dropout}")
+        if self.projector_dropout and not self.projector_hidden_sizes:
+            raise ValueError("projector_dropout needs projector_hidden_sizes: the reference's single-Linear projector has no dropout")
+        return self
 
     def build(self, feature_dims: dict[str, tuple[int, int] | None], n_outputs: int, n_output_timesteps: int) -> nn.Module:
         return FmriEncoder(feature_dims, n_outputs, n_output_timesteps, config=self)
@@ -82,27 +116,36 @@ class FmriEncoder(nn.Module):
         self.projectors = nn.ModuleDict()
         self.contrastive_heads = nn.ModuleDict()
         hidden = self.hidden = config.hidden
-        for modality, tup in feature_dims.items():
+        for index, (modality, tup) in enumerate(feature_dims.items()):
             if tup is None:
                 print(f"Warning: {modality} has no feature dimensions. Skipping projector.")
                 continue
             num_layers, feature_dim = tup
             input_dim = feature_dim * num_layers if config.layer_aggregation == "cat" else feature_dim
             output_dim = hidden // len(feature_dims) if config.feature_aggregation == "cat" else hidden
-            mlp = MlpConfig(norm_layer="layer", activation_layer="gelu", dropout=0.0, hidden_sizes=config.projector_hidden_sizes)
+            mlp = MlpConfig(norm_layer="layer", activation_layer="gelu", dropout=config.projector_dropout,
+                            hidden_sizes=config.projector_hidden_sizes, dropout_backend="hip" if config.projector_dropout else "torch")
             self.projectors[modality] = mlp.build(input_dim, output_dim)
             if config.contrastive_enabled and modality in config.contrastive_modalities:
                 self.contrastive_heads[modality] = mlp.build(input_dim, hidden)
+            for kind, holder in ((SITE_PROJECTOR, self.projectors), (SITE_HEAD, self.contrastive_heads)):
+                if modality in holder and isinstance(holder[modality], Mlp):
+                    holder[modality].dropout_site = (kind << 56) | (index << 16)
         self.combiner = nn.Identity()
         self.predictor = SubjectLayers(in_channels=hidden, out_channels=n_outputs, n_subjects=config.n_subjects,
                                        average_subjects=False, bias=True)
         self.time_pos_embed = nn.Parameter(torch.randn(1, config.max_timesteps, hidden))
         if config.subject_embedding:
             self.subject_embed = nn.Embedding(config.n_subjects, hidden)
-        self.encoder = TransformerEncoderConfig(attn_dropout=0.0, ff_dropout=0.0, layer_dropout=0.0, depth=config.depth,
+        self.encoder = TransformerEncoderConfig(attn_dropout=0.0, ff_dropout=config.ff_dropout, layer_dropout=config.layer_dropout,
+                                                depth=config.depth,
                                                 heads=config.heads, rotary_interleaved=config.rotary_interleaved,
                                                 legacy_scalenorm=config.legacy_scalenorm).build(dim=hidden)
         self._packs = PackCache()
+        self.last_dropout_key: int | None = None          # key of the last training pass with an active HIP dropout
+        self.last_layer_drops: list[bool] | None = None   # its skipped sub-layers (attention, feed-forward per depth); None: layer_dropout 0
+        self._pass_serial = 0
+        self._pass_key: int | None = None
 
     # ------------------------------------------------------------------------------------------
     def _batch_dict(self, batch: SegmentData | dict) -> dict[str, torch.Tensor]:
@@ -124,13 +167,21 @@ class FmriEncoder(nn.Module):
         return self._packs.get(key, [lin.weight, lin.bias], lambda: (ops.pack_weight(f32c(lin.weight)), f32c(lin.bias)))
 
     @staticmethod
-    def _output_linear(proj: nn.Module, packed: torch.Tensor) -> tuple[torch.Tensor, nn.Linear]:
+    def _output_linear(proj: nn.Module, packed: torch.Tensor, drop_key: int | None = None) -> tuple[torch.Tensor, nn.Linear]:
         """(bf16 operand, Linear) of a projector's or contrastive head's last product: the packed features and the module itself for
         the reference's single Linear; with projector_hidden_sizes the hidden blocks (Linear -> LayerNorm -> GELU, HIP) run first and
-        hand over their bf16 [B*T, H_pad] output.  Differentiable where grad is enabled."""
+        hand over their bf16 [B*T, H_pad] output.  Differentiable where grad is enabled.  drop_key: the pass key of an active
+        projector_dropout (training path only)."""
         if isinstance(proj, Mlp):
-            return proj.hidden_operand(packed), proj.blocks()[1]
+            return proj.hidden_operand(packed, drop_key=drop_key), proj.blocks()[1]
         return packed, proj
+
+    def _draw_pass_key(self) -> int | None:
+        """The pass key of the HIP dropouts, drawn only when one is active (so at all-zero settings the RNG stream is untouched)."""
+        if self.encoder.ff_dropout > 0 or self.config.projector_dropout > 0:   # (the encoder module holds its own two rates)
+            self.last_dropout_key = draw_dropout_key()
+            return self.last_dropout_key
+        return None
 
     def _draw_modality_dropout(self) -> list[str]:
         # model.py:133-141 -- same RNG consumption order as the reference
@@ -232,7 +283,11 @@ class FmriEncoder(nn.Module):
         consumes -- takes them when inputs, draw and parameter versions all match, and recomputes otherwise.  The loss is
         bit-identical either way; autograd sums the two branches' gradients at the shared node."""
         dropped = self._draw_modality_dropout()
+        self._pass_key = self._draw_pass_key()
         key = self._latents_key(data, dropped) if share else None
+        if key is not None and (self._pass_key is not None or self.encoder.layer_dropout > 0):
+            self._pass_serial += 1
+            key = key + (self._pass_serial,)   # a stochastic pass: no two have equal latents
         if share == "consume":
             kept, self._shared_latents = getattr(self, "_shared_latents", None), None
             if kept is not None and kept[0] == key and self.config.share_contrastive_latents:
@@ -259,15 +314,16 @@ class FmriEncoder(nn.Module):
             raise RuntimeError(f"The size of tensor a ({self.hidden}) must match the size of tensor b ({self.hidden // n_mod}) "
                                "at non-singleton dimension 2")
         slices = []
+        pkey = self._pass_key if cfg.projector_dropout > 0 else None
         for m in self.feature_dims.keys():
             if m not in self.projectors or m in dropped:  # model.py:143-144,158-159: zero block, no gradient
                 slices.append(torch.zeros(B * T, slot, dtype=torch.float32, device=ref.device))
                 continue
-            packed, lin = self._output_linear(self.projectors[m], self._pack(data[m]))
+            packed, lin = self._output_linear(self.projectors[m], self._pack(data[m]), pkey)
             if lin is self.projectors[m]:
                 slices.append(ag.ProjectorFuse.apply(packed, lin.weight, lin.bias))
             else:   # behind hidden blocks the operand needs its gradient
-                slices.append(ag.Linear.apply(packed, lin.weight, lin.bias, None, None, True))
+                slices.append(self.projectors[m].output(packed, pkey))
         if cat:
             x = torch.cat(slices, dim=1).view(B, T, n_mod * slot)   # model.py:161-162
         else:
@@ -284,20 +340,29 @@ class FmriEncoder(nn.Module):
         cos, sin, neg_sin = enc.rotary_tables(T, x.device)     # neg_sin: the backward's rotation by -theta
         gs, eps = enc.final_norm.gain_scale, enc.final_norm.eps
         scale = enc.dim_head**-0.5
+        # x_transformers' stochastic depth: one random.random() per sub-layer, in layer order, only when layer_dropout > 0
+        drops = [random.random() < enc.layer_dropout for _ in range(2 * enc.depth)] if enc.layer_dropout > 0 else None
+        self.last_layer_drops = drops
+        fkey = self._pass_key if enc.ff_dropout > 0 else None
         for i in range(enc.depth):
             norms_a, attn, res_a = enc.layers[2 * i]
             norms_f, ff, res_f = enc.layers[2 * i + 1]
-            # the block input forks into norm(x) and the scaled residual; ScaleNormFork's backward sums the two gradients in its own kernel
-            xn, xr = ag.ScaleNormFork.apply(x, norms_a[0].g, gs, eps, res_a.residual_scale)
-            qkv = ag.QKVLinear.apply(xn, attn.to_q.weight, attn.to_k.weight, attn.to_v.weight)
-            if enc.rotary_emb_dim:
-                ao, _ = ag.RotaryAttention.apply(qkv, cos, sin, neg_sin, B, T, enc.heads, enc.dim_head, scale, enc.rotary_emb_dim,
-                                                 enc.rotary_interleaved)
-            else:
-                ao = ag.Attention.apply(qkv, B, T, enc.heads, enc.dim_head, scale)
-            x = ag.Linear.apply(ao, attn.to_out.weight, None, xr, res_a.residual_scale, True, True)
-            xn, xr = ag.ScaleNormFork.apply(x, norms_f[0].g, gs, eps, res_f.residual_scale)
-            x = ag.FeedForward.apply(xn, ff.ff[0][0].weight, ff.ff[0][0].bias, ff.ff[2].weight, ff.ff[2].bias, xr, res_f.residual_scale, True)
+            if not (drops and drops[2 * i]):        # a skipped sub-layer leaves x as it is: no norm, no block, no residual scaling
+                # the block input forks into norm(x) and the scaled residual; ScaleNormFork's backward sums the two gradients in its own kernel
+                xn, xr = ag.ScaleNormFork.apply(x, norms_a[0].g, gs, eps, res_a.residual_scale)
+                qkv = ag.QKVLinear.apply(xn, attn.to_q.weight, attn.to_k.weight, attn.to_v.weight)
+                if enc.rotary_emb_dim:
+                    ao, _ = ag.RotaryAttention.apply(qkv, cos, sin, neg_sin, B, T, enc.heads, enc.dim_head, scale, enc.rotary_emb_dim,
+                                                     enc.rotary_interleaved)
+                else:
+                    ao = ag.Attention.apply(qkv, B, T, enc.heads, enc.dim_head, scale)
+                x = ag.Linear.apply(ao, attn.to_out.weight, None, xr, res_a.residual_scale, True, True)
+            if not (drops and drops[2 * i + 1]):
+                xn, xr = ag.ScaleNormFork.apply(x, norms_f[0].g, gs, eps, res_f.residual_scale)
+                args = (xn, ff.ff[0][0].weight, ff.ff[0][0].bias, ff.ff[2].weight, ff.ff[2].bias, xr, res_f.residual_scale, True)
+                if fkey is not None:
+                    args += (ff.ff[1].p, fkey, (SITE_FF << 56) | i)
+                x = ag.FeedForward.apply(*args)
         return x, B, T
 
     def _forward_autograd(self, data: dict[str, torch.Tensor], pool_outputs: bool) -> torch.Tensor:
@@ -362,6 +427,7 @@ class FmriEncoder(nn.Module):
         from modeling_utils import autograd as ag
 
         x, B, T = self._latents_autograd(data, share="consume")
+        hkey = self._pass_key if self.config.projector_dropout > 0 else None   # the contrastive pass's own key
         enc = self.encoder
         brain = ag.ScaleNorm.apply(x, enc.final_norm.g, enc.final_norm.gain_scale, enc.final_norm.eps, True)  # f32 [B*T, H]
         losses: dict[str, torch.Tensor] = {}
@@ -369,11 +435,11 @@ class FmriEncoder(nn.Module):
             if modality not in self.contrastive_heads or modality not in data:
                 continue
             feat = data[modality]
-            packed, head = self._output_linear(self.contrastive_heads[modality], self._pack(feat))
+            packed, head = self._output_linear(self.contrastive_heads[modality], self._pack(feat), hkey)
             if head is self.contrastive_heads[modality]:
                 lat = ag.ProjectorFuse.apply(packed, head.weight, head.bias)        # f32 [B * T_mod, hidden]
             else:
-                lat = ag.Linear.apply(packed, head.weight, head.bias, None, None, True)
+                lat = self.contrastive_heads[modality].output(packed, hkey)
             T_mod = feat.shape[-1]
             if T_mod != T:   # model.py:234-238: adaptive average pool of the modality latents to the brain's time axis
                 lat = lat.view(B, T_mod, -1).transpose(1, 2).contiguous()           # [B, hidden, T_mod]

@@ -193,7 +193,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void scalenorm_bwd_kernel(const float* __restrict__ x, const T* __restrict__ dy,
                                                             const float* __restrict__ g, float gain_scale, float eps, int64_t rows,
                                                             int64_t dim, const float* __restrict__ dres, const float* __restrict__ rs,
-                                                            float* __restrict__ dx, float* __restrict__ dg) {
+                                                            float* __restrict__ dx, float* __restrict__ dg, float* __restrict__ dg_rows) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -218,7 +218,11 @@ __global__ __launch_bounds__(256) void scalenorm_bwd_kernel(const float* __restr
     if (dres) v += dres[row * dim + i] * (rs ? rs[i] : 1.0f);
     dx[row * dim + i] = v;
   }
-  if (dg && lane == 0) atomicAdd(dg, gain_scale * dot * inv);
+  if (dg_rows) {   // the row's term, summed in a fixed order by scalenorm_dg_sum_kernel
+    if (lane == 0) dg_rows[row] = gain_scale * dot * inv;
+  } else if (dg && lane == 0) {
+    atomicAdd(dg, gain_scale * dot * inv);
+  }
 }
 
 // Same with the row of x and dy held in registers (dim = 256 * NV): one pass over HBM, vector accesses, and ONE atomic
@@ -226,7 +230,8 @@ __global__ __launch_bounds__(256) void scalenorm_bwd_kernel(const float* __restr
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void scalenorm_bwd_reg_kernel(const float* __restrict__ x, const T* __restrict__ dy, const float* __restrict__ g,
                                                                 float gain_scale, float eps, int64_t rows, const float* __restrict__ dres,
-                                                                const float* __restrict__ rs, float* __restrict__ dx, float* __restrict__ dg) {
+                                                                const float* __restrict__ rs, float* __restrict__ dx, float* __restrict__ dg,
+                                                                float* __restrict__ dg_rows) {
   __shared__ float dg_part[4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + wv;
@@ -277,11 +282,22 @@ __global__ __launch_bounds__(256) void scalenorm_bwd_reg_kernel(const float* __r
     }
     contrib = gain_scale * dot * inv;
   }
-  if (dg) {
+  if (dg_rows) {
+    if (lane == 0 && row < rows) dg_rows[row] = contrib;
+  } else if (dg) {
     if (lane == 0) dg_part[wv] = contrib;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(dg, dg_part[0] + dg_part[1] + dg_part[2] + dg_part[3]);
   }
+}
+
+// dg[0] = the sum of the per-row terms: one workgroup, every lane its rows in order (f64), then block_sum_d's fixed tree; rounded once
+__global__ __launch_bounds__(1024) void scalenorm_dg_sum_kernel(const float* __restrict__ dg_rows, int64_t rows, float* __restrict__ dg) {
+  __shared__ double sh[16];
+  double s = 0.0;
+  for (int64_t r = threadIdx.x; r < rows; r += 1024) s += (double)dg_rows[r];
+  const double tot = block_sum_d(s, sh);
+  if (threadIdx.x == 0) dg[0] = (float)tot;
 }
 
 __global__ __launch_bounds__(256) void softmax_bwd_kernel(const unsigned short* __restrict__ P, const float* __restrict__ dP,
@@ -631,8 +647,8 @@ extern "C" int tribe_colsum_cast_fwd(const float* a, const float* b, int64_t M, 
   return 0;
 }
 
-extern "C" int tribe_scalenorm_bwd(const float* x, const void* dy, int32_t dy_dtype, const float* g, float gain_scale, float eps,
-                                   int64_t rows, int64_t dim, const float* dres, const float* rs, float* dx, float* dg, void* stream) {
+static int scalenorm_bwd_launch(const float* x, const void* dy, int32_t dy_dtype, const float* g, float gain_scale, float eps, int64_t rows,
+                                int64_t dim, const float* dres, const float* rs, float* dx, float* dg, float* dg_rows, void* stream) {
   TRIBE_REQUIRE(x && dy && g && dx, "tribe_scalenorm_bwd: null pointer");
   TRIBE_REQUIRE(rows > 0 && dim > 0, "tribe_scalenorm_bwd: bad shape");
   dim3 grid((unsigned)((rows + 3) / 4));
@@ -642,21 +658,37 @@ extern "C" int tribe_scalenorm_bwd(const float* x, const void* dy, int32_t dy_dt
 #define TRIBE_SNB(NV)                                                                                                             \
   do {                                                                                                                            \
     if (dy_dtype == TRIBE_F32)                                                                                                    \
-      hipLaunchKernelGGL((scalenorm_bwd_reg_kernel<float, NV>), grid, dim3(256), 0, s, x, (const float*)dy, g, gain_scale, eps, rows, dres, rs, dx, dg); \
+      hipLaunchKernelGGL((scalenorm_bwd_reg_kernel<float, NV>), grid, dim3(256), 0, s, x, (const float*)dy, g, gain_scale, eps, rows, dres, rs, dx, dg, dg_rows); \
     else                                                                                                                          \
       hipLaunchKernelGGL((scalenorm_bwd_reg_kernel<unsigned short, NV>), grid, dim3(256), 0, s, x, (const unsigned short*)dy, g, gain_scale, eps, \
-                         rows, dres, rs, dx, dg);                                                                                 \
+                         rows, dres, rs, dx, dg, dg_rows);                                                                               \
   } while (0)
   if (aligned && dim == 3072) TRIBE_SNB(12);
   else if (aligned && dim == 768) TRIBE_SNB(3);
   else if (dy_dtype == TRIBE_F32)
-    hipLaunchKernelGGL(scalenorm_bwd_kernel<float>, grid, dim3(256), 0, s, x, (const float*)dy, g, gain_scale, eps, rows, dim, dres, rs, dx, dg);
+    hipLaunchKernelGGL(scalenorm_bwd_kernel<float>, grid, dim3(256), 0, s, x, (const float*)dy, g, gain_scale, eps, rows, dim, dres, rs, dx, dg, dg_rows);
   else
     hipLaunchKernelGGL(scalenorm_bwd_kernel<unsigned short>, grid, dim3(256), 0, s, x, (const unsigned short*)dy, g, gain_scale, eps, rows,
-                       dim, dres, rs, dx, dg);
+                       dim, dres, rs, dx, dg, dg_rows);
 #undef TRIBE_SNB
   TRIBE_LAUNCH_CHECK();
+  if (dg_rows) {
+    hipLaunchKernelGGL(scalenorm_dg_sum_kernel, dim3(1), dim3(1024), 0, s, (const float*)dg_rows, rows, dg);
+    TRIBE_LAUNCH_CHECK();
+  }
   return 0;
+}
+
+extern "C" int tribe_scalenorm_bwd(const float* x, const void* dy, int32_t dy_dtype, const float* g, float gain_scale, float eps,
+                                   int64_t rows, int64_t dim, const float* dres, const float* rs, float* dx, float* dg, void* stream) {
+  return scalenorm_bwd_launch(x, dy, dy_dtype, g, gain_scale, eps, rows, dim, dres, rs, dx, dg, nullptr, stream);
+}
+
+extern "C" int tribe_scalenorm_bwd_ordered(const float* x, const void* dy, int32_t dy_dtype, const float* g, float gain_scale, float eps,
+                                           int64_t rows, int64_t dim, const float* dres, const float* rs, float* dx, float* dg, float* dg_rows,
+                                           void* stream) {
+  TRIBE_REQUIRE(dg && dg_rows, "tribe_scalenorm_bwd_ordered: null dg or dg_rows");
+  return scalenorm_bwd_launch(x, dy, dy_dtype, g, gain_scale, eps, rows, dim, dres, rs, dx, dg, dg_rows, stream);
 }
 
 extern "C" int tribe_softmax_bwd(const uint16_t* P, const float* dP, int64_t rows, int64_t T, int64_t T_pad, int64_t ld_p, int64_t ld_dp,

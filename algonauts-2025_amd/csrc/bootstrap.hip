@@ -25,6 +25,7 @@
 // No floating-point atomics anywhere: equal inputs give equal bits.
 #include "common.h"
 #include "lds_sort.h"
+#include "philox.h"
 
 namespace {
 
@@ -35,18 +36,6 @@ constexpr int BP_R = 32;              // replicates per workgroup
 constexpr int BP_V = 64;              // parcels per workgroup
 constexpr int BP_J = 8;               // blocks per LDS stage
 constexpr int BS_LANES = 1024;
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 
 // grid n_boot, dynamic LDS: n_sel int32
 __global__ __launch_bounds__(256) void bootstrap_counts_kernel(unsigned k0, unsigned k1, int n_sel, int* __restrict__ counts) {

@@ -276,12 +276,15 @@ class QKVLinear(torch.autograd.Function):
 
 
 class FeedForward(torch.autograd.Function):
-    """out = gelu(x W1^T + b1) W2^T + b2 + res * res_scale  (x_transformers FeedForward + scaled residual).
-    x bf16 [M, D]; res f32 [M, D] (the block input); out f32 [M, D]."""
+    """out = drop(gelu(x W1^T + b1)) W2^T + b2 + res * res_scale  (x_transformers FeedForward + scaled residual).
+    x bf16 [M, D]; res f32 [M, D] (the block input); out f32 [M, D].  drop: ops.dropout_apply with (p, seed, site) on the bf16 hidden
+    [M, Fh], in place between the two GEMMs; p == 0 (the default) launches nothing.  Backward: the same mask on dpre -- it commutes with
+    the element-wise gelu' of the ACT_GELU_BWD epilogue -- and dW2 from the saved, dropped hidden."""
 
     @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, res, res_scale, raw_res_grad: bool = False):
+    def forward(ctx, x, w1, b1, w2, b2, res, res_scale, raw_res_grad: bool = False, p: float = 0.0, seed: int = 0, site: int = 0):
         ctx.raw_res_grad = raw_res_grad   # see Linear
+        ctx.drop = (float(p), int(seed), int(site))
         M, D = x.shape
         Fh = w1.shape[0]
         w1p, _ = PACKS.get(w1)
@@ -289,6 +292,8 @@ class FeedForward(torch.autograd.Function):
         pre = torch.empty(M, Fh, dtype=torch.bfloat16, device=x.device)
         h = torch.empty(M, Fh, dtype=torch.bfloat16, device=x.device)
         _gemm(x, w1p, h, lda=D, ldb=D, ldc=Fh, M=M, N=Fh, K=D, bias=b1, act=_lib.ACT_GELU, aux=pre, role=ROLE["ff1"])
+        if p > 0:
+            ops.dropout_apply(h, p, seed, site, out=h)
         out = torch.empty(M, D, dtype=torch.float32, device=x.device)
         _gemm(h, w2p, out, lda=Fh, ldb=Fh, ldc=D, M=M, N=D, K=Fh, bias=b2, res=res, res_scale=res_scale, role=ROLE["ff2"])
         ctx.save_for_backward(x, w1, w2, pre, h, res, res_scale)
@@ -305,11 +310,19 @@ class FeedForward(torch.autograd.Function):
         _, w2t = PACKS.get(w2)                                  # [Fh, D]
         dpre = torch.empty(M, Fh, dtype=torch.bfloat16, device=x.device)
         _gemm(dob, w2t, dpre, lda=D, ldb=D, ldc=Fh, M=M, N=Fh, K=D, act=_lib.ACT_GELU_BWD, aux=pre)   # dh * gelu'(pre)
+        if ctx.drop[0] > 0:
+            ops.dropout_apply(dpre, *ctx.drop, out=dpre)
         dw2 = torch.empty(D, Fh, dtype=torch.float32, device=x.device)
         wgrad(dob, h, dw2, M, D, Fh, D, Fh)
         db1 = colsum(dpre, M, Fh)
         dx, dw1 = dense_bwd(dpre, x, PACKS.get(w1)[1], Fh)      # (no pad: ff_inner % 64 == 0)
-        return dx, dw1, db1, dw2, db2, dres, drs, None
+        return dx, dw1, db1, dw2, db2, dres, drs, None, None, None, None
+
+
+def _dg_buffers(rows: int, device: torch.device) -> tuple[torch.Tensor, torch.Tensor]:
+    """(dg f32 [1], per-row staging f32 [rows]) of tribe_scalenorm_bwd_ordered: the gain gradient is the fixed-order sum of the rows' terms
+    (the atomic sum of tribe_scalenorm_bwd differs in its last bits from run to run, which a seeded dropout run must not)."""
+    return torch.empty(1, dtype=torch.float32, device=device), torch.empty(rows, dtype=torch.float32, device=device)
 
 
 class ScaleNorm(torch.autograd.Function):
@@ -328,9 +341,9 @@ class ScaleNorm(torch.autograd.Function):
         dy = dy.contiguous()
         M, D = x.shape
         dx = torch.empty_like(x)
-        dg = torch.zeros(1, dtype=torch.float32, device=x.device)
-        check(lib().tribe_scalenorm_bwd(x.data_ptr(), dy.data_ptr(), _DT[dy.dtype], g.data_ptr(), ctx.gs, ctx.eps, M, D, None, None,
-                                        dx.data_ptr(), dg.data_ptr(), _s()), "tribe_scalenorm_bwd")
+        dg, dg_rows = _dg_buffers(M, x.device)
+        check(lib().tribe_scalenorm_bwd_ordered(x.data_ptr(), dy.data_ptr(), _DT[dy.dtype], g.data_ptr(), ctx.gs, ctx.eps, M, D, None, None,
+                                                dx.data_ptr(), dg.data_ptr(), dg_rows.data_ptr(), _s()), "tribe_scalenorm_bwd_ordered")
         return dx, dg, None, None, None
 
 
@@ -351,15 +364,16 @@ class ScaleNormFork(torch.autograd.Function):
     def backward(ctx, dy, dxr):
         x, g, rs = ctx.saved_tensors
         M, D = x.shape
-        dx = torch.empty_like(x)
-        dg = torch.zeros(1, dtype=torch.float32, device=x.device)
         if dy is None:    # the normed branch was not used: only the residual gradient flows
             dx = dxr if rs is None else dxr * rs
             return dx, None, None, None, None
+        dx = torch.empty_like(x)
+        dg, dg_rows = _dg_buffers(M, x.device)
         dy = dy.contiguous()
         dres = None if dxr is None else dxr.float().contiguous()
-        check(lib().tribe_scalenorm_bwd(x.data_ptr(), dy.data_ptr(), _DT[dy.dtype], g.data_ptr(), ctx.gs, ctx.eps, M, D, ops._p(dres),
-                                        None if dres is None else ops._p(rs), dx.data_ptr(), dg.data_ptr(), _s()), "tribe_scalenorm_bwd")
+        check(lib().tribe_scalenorm_bwd_ordered(x.data_ptr(), dy.data_ptr(), _DT[dy.dtype], g.data_ptr(), ctx.gs, ctx.eps, M, D, ops._p(dres),
+                                                None if dres is None else ops._p(rs), dx.data_ptr(), dg.data_ptr(), dg_rows.data_ptr(), _s()),
+              "tribe_scalenorm_bwd_ordered")
         return dx, dg, None, None, None
 
 
@@ -728,6 +742,40 @@ class NormAct(torch.autograd.Function):
         dz, dgamma, dbeta = ops.norm_act_bwd(dy if dy.stride(-1) == 1 else dy.contiguous(), z, mean, rstd, gamma, beta, ctx.act, norm=ctx.norm,
                                              param_grads=want)
         return dz, dgamma if gamma is not None else None, dbeta if beta is not None else None, None, None, None
+
+
+class Dropout(torch.autograd.Function):
+    """y = ops.dropout_apply(x, p, seed, site): x f32 or bf16 [M, W]; the mask covers the leading `dim` columns (default W; a K-padded
+    operand [M, N_pad64] passes dim = N, its pad columns stay as they are).  Out of place by default.  inplace: x is overwritten and
+    handed back (ctx.mark_dirty) -- only for a tensor no other function saved, such as NormAct's or Linear's fresh output.
+    backward = dropout_apply(dy, same p / seed / site), a new tensor whose columns >= dim are zero."""
+
+    @staticmethod
+    def forward(ctx, x, p: float, seed: int, site: int, dim: int | None = None, inplace: bool = False):
+        W = x.shape[1]
+        dim = W if dim is None else int(dim)
+        if not 0 < dim <= W:
+            raise ValueError(f"Dropout: dim={dim} outside (0, {W}]")
+        ctx.key, ctx.dim = (float(p), int(seed), int(site)), dim
+        if inplace:
+            ctx.mark_dirty(x)
+            if p > 0:
+                ops.dropout_apply(x[:, :dim], p, seed, site, out=x[:, :dim])
+            return x
+        x = x.contiguous()
+        y = torch.empty_like(x) if dim == W else torch.zeros_like(x)
+        ops.dropout_apply(x[:, :dim], p, seed, site, out=y[:, :dim])
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        dim = ctx.dim
+        if dy.stride(-1) != 1:
+            dy = dy.contiguous()
+        dx = torch.empty_like(dy, memory_format=torch.contiguous_format) if dim == dy.shape[1] else \
+            torch.zeros_like(dy, memory_format=torch.contiguous_format)
+        ops.dropout_apply(dy[:, :dim], *ctx.key, out=dx[:, :dim])
+        return dx, None, None, None, None, None
 
 
 class PackRows(torch.autograd.Function):

@@ -116,6 +116,9 @@ class MlpConfig(pydantic.BaseModel):
     activation_layer: tp.Literal["relu", "gelu", "elu", "prelu", None] = "relu"
     bias: bool = True
     dropout: float = 0.0
+    # Not in the reference: who runs an ACTIVE dropout (training, p > 0) of the returned Mlp on the GPU.  "torch": the stock f32 modules
+    # with torch's generator (masks and route as they always were); "hip": the HIP route with counter-based masks (Mlp docstring)
+    dropout_backend: tp.Literal["torch", "hip"] = "torch"
 
     def build(self, input_size: int | None = None, output_size: int | None = None) -> nn.Module:
         input_size = self.input_size if input_size is None else input_size
@@ -137,11 +140,21 @@ class MlpConfig(pydantic.BaseModel):
             layers += [act(), nn.Dropout(self.dropout)]
             width = h
         layers += [nn.Linear(width, sizes[-1], bias=self.bias), nn.Dropout(self.dropout)]
-        return Mlp(layers, self.norm_layer, self.activation_layer, self.dropout)
+        if self.dropout_backend == "hip" and not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"MlpConfig: dropout_backend='hip' needs 0 <= dropout < 1, got {self.dropout}")
+        return Mlp(layers, self.norm_layer, self.activation_layer, self.dropout, self.dropout_backend)
 
 
 _NORMS: dict[str | None, tp.Any] = {"layer": nn.LayerNorm, "batch": nn.BatchNorm1d, "instance": nn.InstanceNorm1d, None: None}
 _ACTIVATIONS: dict[str | None, tp.Any] = {"relu": nn.ReLU, "gelu": nn.GELU, "elu": nn.ELU, "prelu": nn.PReLU, None: nn.Identity}
+
+
+MLP_OUT_BLOCK = 0xFFFF   # the block number of an Mlp's output dropout in its site numbering (hidden blocks count from 0)
+
+
+def draw_dropout_key() -> int:
+    """One 63-bit key of the counter-based dropout masks from torch's default CPU generator (torch.manual_seed reproduces it)."""
+    return int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64).item())
 
 
 class Mlp(nn.Sequential):
@@ -149,20 +162,34 @@ class Mlp(nn.Sequential):
     docstring), so parameters, `state_dict()` and the CPU forward are those of the reference's module.
 
     forward(x[..., in], f32 or bf16) -> f32 [..., out] has two routes:
-      * HIP: x on the GPU, norm None or "layer", activation relu / gelu / elu / None, dropout inactive (p == 0 or eval mode).  Every
-        Linear is the bf16 MFMA GEMM with f32 output, norm + activation one row kernel (modeling_utils.autograd.NormAct); with grad
-        enabled the route is differentiable through the HIP backward kernels.
-      * stock: everything else runs nn.Sequential.forward unchanged (CPU tensors, "batch" / "instance" norms, PReLU, active dropout).
-    `hip_calls` / `stock_calls` count the forwards each route served."""
+      * HIP: x on the GPU, norm None or "layer", activation relu / gelu / elu / None, dropout inactive (p == 0 or eval mode) or
+        dropout_backend == "hip".  Every Linear is the bf16 MFMA GEMM with f32 output, norm + activation one row kernel
+        (modeling_utils.autograd.NormAct); with grad enabled the route is differentiable through the HIP backward kernels.
+      * stock: everything else runs nn.Sequential.forward unchanged (CPU tensors, "batch" / "instance" norms, PReLU, active dropout
+        under dropout_backend == "torch").
+    `hip_calls` / `stock_calls` count the forwards each route served.
 
-    def __init__(self, layers: tp.Sequence[nn.Module], norm_layer: str | None, activation_layer: str | None, dropout: float):
+    Active dropout on the HIP route (dropout_backend "hip", training, p > 0) stands where torchvision's Dropout modules stand: after every
+    hidden activation, on the bf16 operand [M, H_pad64] over its H logical columns, and after the last Linear on its f32 output
+    (tribe_dropout_apply, in place on tensors the route owns; the backward applies the same mask to the gradient).  `forward` draws one
+    64-bit key per call from torch's default CPU generator and keeps it as `last_dropout_key`; hidden block i uses site
+    `dropout_site + i`, the output `dropout_site + MLP_OUT_BLOCK`.  The masks are not torch's: a different stream, and a dropped
+    element is +0.0 whatever it held."""
+
+    def __init__(self, layers: tp.Sequence[nn.Module], norm_layer: str | None, activation_layer: str | None, dropout: float,
+                 dropout_backend: str = "torch"):
         super().__init__(*layers)
-        self.norm_layer, self.activation_layer, self.dropout = norm_layer, activation_layer, dropout
+        self.norm_layer, self.activation_layer, self.dropout, self.dropout_backend = norm_layer, activation_layer, dropout, dropout_backend
         self.hip_calls = self.stock_calls = 0
+        self.dropout_site = 0                       # site of hidden block 0 (FmriEncoder numbers its projectors and heads: model.py)
+        self.last_dropout_key: int | None = None
 
     def hip_supported(self) -> bool:
         return (self.norm_layer in (None, "layer") and self.activation_layer in ops.NORM_ACT_ACTS
-                and (self.dropout == 0 or not self.training))
+                and (self.dropout == 0 or not self.training or self.dropout_backend == "hip"))
+
+    def hip_dropout_active(self) -> bool:
+        return self.dropout_backend == "hip" and self.dropout > 0 and self.training
 
     def blocks(self) -> tuple[list[tuple[nn.Linear, nn.LayerNorm | None]], nn.Linear]:
         """([(Linear, its LayerNorm or None) per hidden size], the last Linear)."""
@@ -171,9 +198,10 @@ class Mlp(nn.Sequential):
         hidden = [(mods[i], mods[i + 1] if isinstance(mods[i + 1], nn.LayerNorm) else None) for i in linears[:-1]]
         return hidden, mods[linears[-1]]
 
-    def hidden_operand(self, packed: torch.Tensor, input_grad: bool = False) -> torch.Tensor:
+    def hidden_operand(self, packed: torch.Tensor, input_grad: bool = False, drop_key: int | None = None) -> torch.Tensor:
         """The hidden blocks on a packed bf16 [M, K_pad64] input -> the bf16 [M, H_pad64] operand of the last Linear.  input_grad: the
-        input itself needs a gradient (a feature does not: then the first Linear computes none)."""
+        input itself needs a gradient (a feature does not: then the first Linear computes none).  drop_key: the pass key of an active
+        HIP dropout (None: no dropout)."""
         from .. import autograd as ag
 
         a = packed
@@ -186,7 +214,19 @@ class Mlp(nn.Sequential):
                 a = ag.NormAct.apply(z, None, None, 0.0, self.activation_layer, False)
             else:
                 a = ag.NormAct.apply(z, norm.weight, norm.bias, norm.eps, self.activation_layer, True)
+            if drop_key is not None:
+                a = ag.Dropout.apply(a, self.dropout, drop_key, self.dropout_site + i, lin.out_features, True)
         return a
+
+    def output(self, operand: torch.Tensor, drop_key: int | None = None) -> torch.Tensor:
+        """The last Linear on hidden_operand's result -> f32 [M, out], followed by the output dropout when drop_key is given."""
+        from .. import autograd as ag
+
+        last = self.blocks()[1]
+        out = ag.Linear.apply(operand, last.weight, last.bias, None, None, True)
+        if drop_key is not None:
+            out = ag.Dropout.apply(out, self.dropout, drop_key, self.dropout_site + MLP_OUT_BLOCK, None, True)
+        return out
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not (x.is_cuda and self.hip_supported()):
@@ -197,8 +237,9 @@ class Mlp(nn.Sequential):
         self.hip_calls += 1
         if x.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"Mlp: expected an f32 or bf16 input, got {x.dtype}")
-        last = self.blocks()[1]
+        key = None
+        if self.hip_dropout_active():
+            key = self.last_dropout_key = draw_dropout_key()
         input_grad = torch.is_grad_enabled() and x.requires_grad
-        a = self.hidden_operand(ag.PackRows.apply(x.reshape(-1, x.shape[-1])), input_grad)
-        out = ag.Linear.apply(a, last.weight, last.bias, None, None, True)
+        out = self.output(self.hidden_operand(ag.PackRows.apply(x.reshape(-1, x.shape[-1])), input_grad, key), key)
         return out.view(*x.shape[:-1], out.shape[-1])

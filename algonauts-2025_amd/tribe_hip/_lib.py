@@ -223,6 +223,7 @@ SIGNATURES = {
     "tribe_transpose_bf16_b2": (C.c_int, [vp, i32, i64, i64, i64, i64, i64, i64, i64, vp, i64, i64, vp]),
     "tribe_colsum_fwd": (C.c_int, [vp, i32, vp, i64, i64, i64, vp, i32, vp]),
     "tribe_scalenorm_bwd": (C.c_int, [vp, vp, i32, vp, f32, f32, i64, i64, vp, vp, vp, vp, vp]),
+    "tribe_scalenorm_bwd_ordered": (C.c_int, [vp, vp, i32, vp, f32, f32, i64, i64, vp, vp, vp, vp, vp, vp]),
     "tribe_softmax_bwd": (C.c_int, [vp, vp, i64, i64, i64, i64, i64, f32, vp, i64, vp]),
     "tribe_softmax_fwd": (C.c_int, [vp, i64, i64, i64, vp, i64, i64, vp]),
     "tribe_mse_bwd": (C.c_int, [vp, vp, i64, vp, vp, vp]),
@@ -254,6 +255,8 @@ SIGNATURES = {
     "tribe_norm_act_bwd_workspace_bytes": (sz, [i64, i64]),
     "tribe_norm_act_bwd": (C.c_int, [vp, i32, i64, vp, i64, i64, i64, vp, vp, vp, vp, i32, i32, vp, i32, i64, vp, vp, vp, sz, vp]),
     "tribe_norm_act_path": (C.c_int, [vp, i64, i64, vp, vp, vp, i32, i64, vp, i32, i64]),
+    "tribe_dropout_apply": (C.c_int, [vp, vp, i32, i64, i64, i64, i64, C.c_uint32, f32, C.c_uint64, C.c_uint64, vp]),
+    "tribe_dropout_path": (C.c_int, [vp, vp, i32, i64, i64, i64]),
     "tribe_quantize_fp8_fwd": (C.c_int, [vp, i32, i64, i64, i64, f32, vp, i64, vp]),
     "tribe_norm_quantize_fp8_fwd": (C.c_int, [vp, i64, i64, vp, vp, i32, f32, f32, vp, vp]),
     "tribe_absmax_fwd": (C.c_int, [vp, i32, i64, i64, i64, vp, i32, vp]),

@@ -434,6 +434,57 @@ def norm_act_path(z: torch.Tensor, gamma: torch.Tensor | None, beta: torch.Tenso
                                                     _p(dy), 0 if dy is None else _DT[dy.dtype], ld_dy)]
 
 
+# dropout with a counter-based mask (csrc/dropout.hip)
+DROPOUT_PATHS = ("vec16", "vec8", "elem")                 # tribe_dropout_path's codes
+
+
+def dropout_params(p: float) -> tuple[int, _np.float32]:
+    """(threshold, scale) of tribe_dropout_apply for drop probability p: an element is kept iff its Philox word >= threshold =
+    trunc(p * 2^32); kept values are multiplied by scale = float32(1 / (1 - p))."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout: p must satisfy 0 <= p < 1, got {p}")
+    return int(p * 4294967296.0), _np.float32(1.0 / (1.0 - p))
+
+
+def dropout_apply(x: torch.Tensor, p: float, seed: int, site: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """y = keep ? x * scale : +0.0 for x f32 or bf16 [rows, dim] with contiguous rows (a column slice of a wider buffer is fine: the mask
+    is indexed by (row, column, dim), never by the pitch).  Element (r, c) is kept iff word (r * dim + c) & 3 of Philox4x32-10 with
+    counter ((r * dim + c) >> 2, site) and key `seed` is >= trunc(p * 2^32).  A dropped NaN or negative value is +0.0 (a select, where
+    torch.dropout multiplies).  `out`: same shape and dtype, rows contiguous; `out is x` works in place; None = a new contiguous
+    tensor.  The backward of dropout is this call on the gradient with the same (p, seed, site).  p == 0 launches nothing: x itself
+    (or `out` after a copy) comes back."""
+    threshold, scale = dropout_params(p)
+    rows, dim, ld_x = _row_view(x, (torch.float32, torch.bfloat16), "x")
+    for name, v in (("seed", seed), ("site", site)):
+        if not 0 <= int(v) < 1 << 64:
+            raise ValueError(f"dropout_apply: {name} must fit 64 unsigned bits, got {v}")
+    ld_y = ld_x
+    if out is not None and out is not x:
+        ld_y = _row_view(out, x.dtype, "out", rows, dim)[2]
+        if out.shape[1] != dim:
+            raise ValueError(f"dropout_apply: out {tuple(out.shape)} must have the shape of x {tuple(x.shape)}")
+    if p == 0.0:
+        if out is None or out is x:
+            return x
+        out.copy_(x)
+        return out
+    if out is None:
+        out = torch.empty(rows, dim, dtype=x.dtype, device=x.device)
+        ld_y = dim
+    check(lib().tribe_dropout_apply(x.data_ptr(), out.data_ptr(), _DT[x.dtype], rows, dim, ld_x, ld_y, threshold, float(scale), int(seed),
+                                    int(site), _stream()), "tribe_dropout_apply")
+    return out
+
+
+def dropout_path(x: torch.Tensor, out: torch.Tensor | None = None) -> str:
+    """Name of the kernel tribe_dropout_apply picks for these tensors (out None: in place)."""
+    _, dim, ld_x = _row_view(x, (torch.float32, torch.bfloat16), "x")
+    ld_y = ld_x if out is None else _row_view(out, x.dtype, "out")[2]
+    y = x if out is None else out
+    return DROPOUT_PATHS[lib().tribe_dropout_path(x.data_ptr(), y.data_ptr(), _DT[x.dtype], dim, ld_x, ld_y)]
+
+
 def embedding(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     _cuda(table, (torch.float32, torch.bfloat16), "table")
     _cuda(ids, torch.int64, "ids")

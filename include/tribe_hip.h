@@ -591,6 +591,10 @@ int tribe_colsum_fwd(const void* a, int32_t a_dtype, const float* b, int64_t M, 
  * dy bf16 or f32 [M, dim]; dres / dx f32 (may alias). */
 int tribe_scalenorm_bwd(const float* x, const void* dy, int32_t dy_dtype, const float* g, float gain_scale, float eps,
                         int64_t rows, int64_t dim, const float* dres, const float* rs, float* dx, float* dg, void* stream);
+/* The same with a reproducible gain gradient: every row's term gain_scale * <xhat, dy> is staged in dg_rows (f32 [rows]) and a second launch
+ * WRITES dg[0] = their sum in a fixed order (f64, rounded once) -- no atomics, equal inputs give equal bits.  dg and dg_rows are required. */
+int tribe_scalenorm_bwd_ordered(const float* x, const void* dy, int32_t dy_dtype, const float* g, float gain_scale, float eps, int64_t rows,
+                                int64_t dim, const float* dres, const float* rs, float* dx, float* dg, float* dg_rows, void* stream);
 /* dS = P * (dP - rowsum(P * dP)) * scale   (softmax backward; P bf16, dP f32, dS bf16; row strides ld_p, ld_dp, ld_ds;
  * columns >= T of dS are zero-filled up to T_pad) */
 int tribe_softmax_bwd(const uint16_t* P, const float* dP, int64_t rows, int64_t T, int64_t T_pad, int64_t ld_p, int64_t ld_dp,
@@ -839,6 +843,22 @@ int tribe_norm_act_bwd(const void* dy, int32_t dy_dtype, int64_t ld_dy, const fl
  * a multiple of four elements).  dy / dz NULL: the forward's choice for (z, y); else the backward's for (dy, z, dz). */
 int tribe_norm_act_path(const float* z, int64_t dim, int64_t ld_z, const float* gamma, const float* beta, const void* y, int32_t y_dtype,
                         int64_t ld_y, const void* dy, int32_t dy_dtype, int64_t ld_dy);
+
+/* ---- dropout with a counter-based mask (ff_dropout, Mlp dropout; csrc/dropout.hip) ----
+ * y = keep(r, c) ? x * scale : +0.0 over the logical [rows, dim] tensor (f32 or bf16, row pitches ld_x / ld_y >= dim, x == y allowed;
+ * any other overlap is undefined).  Element (r, c) has idx = r * dim + c (64-bit, from dim and never from a pitch); its random word is
+ * word idx & 3 of Philox4x32-10 with counter (lo32(idx >> 2), hi32(idx >> 2), lo32(site), hi32(site)) and key (lo32(seed),
+ * hi32(seed)); it is kept iff word >= threshold.  The host passes threshold = trunc(p * 2^32) and scale = (float)(1 / (1 - p)).
+ * Kept: one f32 multiply, rounded to nearest (bf16: widened, multiplied in f32, rounded to nearest even).  Dropped: +0.0 by a select --
+ * a dropped NaN, infinity or negative value is +0.0, where torch.dropout's multiply by zero gives NaN or -0.0.  Columns >= dim are
+ * neither read nor written.  The backward of dropout is this call on the gradient with the same (threshold, scale, seed, site).
+ * Integer-exact mask, no atomics: the result depends on (seed, site, r, c, dim, threshold, scale) alone.
+ * Errors (< 0, nothing launched): null pointer, dtype, rows / dim <= 0, ld < dim, scale not in [1, FLT_MAX]. */
+int tribe_dropout_apply(const void* x, void* y, int32_t dtype /* TRIBE_F32 | TRIBE_BF16 */, int64_t rows, int64_t dim, int64_t ld_x,
+                        int64_t ld_y, uint32_t threshold, float scale, uint64_t seed, uint64_t site, void* stream);
+/* Which kernel the launcher picks: 0 = 16-byte accesses (four f32 / eight bf16: dim and both pitches multiples of that, both pointers
+ * 16-byte aligned), 1 = 8-byte accesses (four bf16 where 0 does not fit: multiples of four, 8-byte aligned), 2 = element accesses. */
+int tribe_dropout_path(const void* x, const void* y, int32_t dtype, int64_t dim, int64_t ld_x, int64_t ld_y);
 
 #ifdef __cplusplus
 }
