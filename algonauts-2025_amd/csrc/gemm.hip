@@ -19,12 +19,12 @@
 // chunk ^= (row & 7) is applied to the per-lane SOURCE address and undone on the ds_read_b128
 // fragment read (guide rule 21 / T2).  Roofline: MFMA (dense bf16) -- see DESIGN.md "Kernels".
 #include "gemm_common.h"
+#include "gemm_plan.h"
 
 namespace {
 
-constexpr int BK = 64;
+constexpr int BK = tribe_gemm_detail::K_STEP;
 typedef __attribute__((ext_vector_type(4))) short s16x4_tn;   // operand of ds_read_b64_tr_b16
-constexpr int TRIBE_ROLE_EXT = 100;  // kernel instantiation carrying the extended epilogue (see gemm_common.h)
 
 // =============================================================================================
 // 256 x 256 x 64, counted-vmcnt pipeline
@@ -82,16 +82,10 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // leaves its accumulators in the workspace (slot 2 w + part, 256 KiB, in register order: 1 KiB per store instruction) and
 // streamk_reduce_kernel, launched behind it, sums the parts of every split tile IN ORDER (deterministic) and writes alpha * sum to C.
 // (First version: f32 atomics into a zeroed C -- the chip sustains only ~0.65 TB/s of them, ~100 us per 256-KiB part when every CU adds at
-// once; profiles/r03_z11_gemm_streamk.txt.)  dW of out-proj at B = 16: 144 tiles = 0.56 rounds -> 256 CUs busy.
-struct SkSched {
-  int tiles_dp;   // tiles (linear index < tiles_dp) computed whole; >= tiles_m * tiles_n: no stream-K
-  int rem_units;  // K-steps of the stream-K region: (tiles - tiles_dp) * nk
-  int q;          // K-steps per worker
-  int workers;
-  float* ws;      // 2 * workers slots of 256 x 256 f32
-  unsigned short second_worker[256];
-};
-constexpr int SK_SLOT_FLOATS = 256 * 256;
+// once; profiles/r03_z11_gemm_streamk.txt.)  Only remainders of up to half a round are cut (plan_stream_k, gemm_plan.cpp): dW of FF1 / FF2 at
+// B = 16 (576 tiles, remainder 64) and of the projectors (64 tiles); dW of out-proj (144 tiles) and of QKV (remainder 176) measured slower split.
+// The fields live in SkSchedule (gemm_plan.h), which the host planner fills; this is the kernels' parameter type.
+struct SkSched : SkSchedule {};
 
 template <int OUT_BF16, int ROLE, int TN = 0, int NB = 4>
 __global__ __launch_bounds__(512, 2) void gemm_nt_256x256x64(const tribe_gemm_desc g, int tiles_m, int tiles_n, const SkSched sk) {
@@ -1172,8 +1166,10 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_4w256(const tribe_gemm_desc g,
 // Launch tables.  gemm.hip is compiled in four parts (Makefile: -DTRIBE_GEMM_PART=0 .. 3 -> gemm.o, gemm_p1.o, gemm_p2.o, gemm_p3.o) so that
 // the instantiations build side by side: part 0 = the C entry points + the 8-wave 256 x 256 kernel (and its transposed-operand form),
 // part 1 = the 256 x 192 kernel, part 2 = the two 128 x 128 kernels, part 3 = the 4-wave 256 x 256 kernel.  A build without the macro compiles everything in one unit.
+// Which table a launch goes through, and with which pair, grid and schedule, is decided in gemm_plan.cpp (host code only, no kernel:
+// gemm_resolve); the list of pairs, TRIBE_GEMM_PAIRS, lives in gemm_plan.h.
 // ROLE gives each call site of the path its own kernel symbol, so that rocprofv3 --stats reports per-operator rows; in the 8-wave NT kernel the
-// four encoder roles (QKV, FF1, OUT_PROJ, FF2) also compile the epilogue of exactly their operator set (epilogue_role, launcher: role8_ok).
+// four encoder roles (QKV, FF1, OUT_PROJ, FF2) also compile the epilogue of exactly their operator set (epilogue_role, planner: role8_ok).
 // ---------------------------------------------------------------------------------------------
 #ifndef TRIBE_GEMM_PART
 #define TRIBE_GEMM_PART -1
@@ -1181,12 +1177,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_4w256(const tribe_gemm_desc g,
 #define TRIBE_GEMM_HAS_PART(p) (TRIBE_GEMM_PART < 0 || TRIBE_GEMM_PART == (p))
 
 namespace tribe_gemm_detail {
-enum { KIND_SMALL = 0, KIND_BIG = 1, KIND_RING = 2, KIND_BIG4W = 3 };
-// (output dtype, role symbol) pairs that exist as kernels; every other combination runs under the GENERIC symbol
-#define TRIBE_GEMM_PAIRS(X)                                                                                            \
-  X(0, 1, TRIBE_ROLE_GENERIC) X(1, 0, TRIBE_ROLE_GENERIC) X(2, 1, TRIBE_ROLE_EXT) X(3, 0, TRIBE_ROLE_EXT)              \
-  X(4, 0, TRIBE_ROLE_PROJECTOR) X(5, 1, TRIBE_ROLE_QKV) X(6, 0, TRIBE_ROLE_ATTN_SCORES) X(7, 1, TRIBE_ROLE_ATTN_PV)    \
-  X(8, 0, TRIBE_ROLE_OUT_PROJ) X(9, 1, TRIBE_ROLE_FF1) X(10, 0, TRIBE_ROLE_FF2) X(11, 0, TRIBE_ROLE_VOXEL_HEAD)
 void launch_big4(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n);
 void launch_big4_tn(int bf, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n, const SkSched& sk);
 void launch_big3(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n);
@@ -1195,21 +1185,12 @@ void launch_splitk_epilogue(int bf, hipStream_t s, const tribe_gemm_desc* d, int
 void launch_4w(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n);
 void launch_small(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n);
 
-// the dynamic-LDS attribute is set once per kernel AND device (one process may drive several GPUs)
-template <auto KERNEL, int THREADS, int SMEM, class... Extra>
-static void launch_k(dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n, const Extra&... extra) {
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
-  hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS, 1, 1), SMEM, s, *d, tiles_m, tiles_n, extra...);
-}
-inline const SkSched& no_stream_k() {
-  static const SkSched none = [] { SkSched k{}; k.tiles_dp = 0x7fffffff; return k; }();
-  return none;
+// a planned schedule as the kernels' parameter, its parts travelling through the workspace `ws`
+inline SkSched kernel_arg(const SkSchedule& plan, void* ws = nullptr) {
+  SkSched k{};
+  static_cast<SkSchedule&>(k) = plan;
+  k.ws = (float*)ws;
+  return k;
 }
 #define TRIBE_GEMM_TABLE(NAME)                                                                                         \
   void NAME(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n) {                  \
@@ -1220,7 +1201,7 @@ inline const SkSched& no_stream_k() {
   }
 #if TRIBE_GEMM_HAS_PART(0)
 #define TRIBE_GEMM_CASE_launch_big4(idx, bf, role) \
-  case idx: launch_k<gemm_nt_256x256x64<bf, role, 0, 4>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, no_stream_k()); break;
+  case idx: launch_k<gemm_nt_256x256x64<bf, role, 0, 4>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, kernel_arg(no_stream_k())); break;
 TRIBE_GEMM_TABLE(launch_big4)
 void launch_big4_tn(int bf, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n, const SkSched& sk) {
   if (bf) launch_k<gemm_nt_256x256x64<1, TRIBE_ROLE_GENERIC, 1, 4>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, sk);
@@ -1229,7 +1210,7 @@ void launch_big4_tn(int bf, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, 
 #endif
 #if TRIBE_GEMM_HAS_PART(1)
 #define TRIBE_GEMM_CASE_launch_big3(idx, bf, role) \
-  case idx: launch_k<gemm_nt_256x256x64<bf, role, 0, 3>, 512, 2 * (big::A_BYTES + 192 * BK * 2)>(grid, s, d, tiles_m, tiles_n, no_stream_k()); break;
+  case idx: launch_k<gemm_nt_256x256x64<bf, role, 0, 3>, 512, 2 * (big::A_BYTES + 192 * BK * 2)>(grid, s, d, tiles_m, tiles_n, kernel_arg(no_stream_k())); break;
 TRIBE_GEMM_TABLE(launch_big3)
 #endif
 #if TRIBE_GEMM_HAS_PART(2)
@@ -1257,10 +1238,9 @@ extern "C" int tribe_debug_4w(unsigned long long* out) { return (int)hipMemcpyFr
 #endif
 void launch_4w(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n) {
   switch (pair) {   // the four encoder GEMMs with compile-time operator sets (epilogue_w4)
-    case 5: launch_k<gemm_nt_4w256<1, TRIBE_ROLE_QKV>, 256, w4::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
-    case 8: launch_k<gemm_nt_4w256<0, TRIBE_ROLE_OUT_PROJ>, 256, w4::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
-    case 9: launch_k<gemm_nt_4w256<1, TRIBE_ROLE_FF1>, 256, w4::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
-    case 10: launch_k<gemm_nt_4w256<0, TRIBE_ROLE_FF2>, 256, w4::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
+#define TRIBE_GEMM_CASE_launch_4w(idx, bf, role) \
+    case idx: launch_k<gemm_nt_4w256<bf, role>, 256, w4::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
+    TRIBE_GEMM_ROLE_PAIRS(TRIBE_GEMM_CASE_launch_4w)
     default: break;
   }
 }
@@ -1371,127 +1351,13 @@ extern "C" int tribe_rownorm_scale_fwd(const float* partial, int64_t rows, int64
 }
 
 
-#ifndef TRIBE_GEMM_4W_DEFAULT
-#define TRIBE_GEMM_4W_DEFAULT 0   // see gemm_plan: after the 8-wave kernel took over its epilogue techniques the two tie; tile_hint 5 selects it
-#endif
-namespace tribe_gemm_detail {
-// Which kernel and tile a launch gets.  sumsq_cols = columns per row_sumsq slot (one slot per wave column group).
-struct GemmPlan { int kind, bm, bn, sumsq_cols; int splits = 1; };
-// true when the descriptor carries exactly the operator set epilogue_w4 compiles for its role (and the alignments its vector accesses need)
-static bool w4_role_ok(const tribe_gemm_desc* d) {
-  const bool res_role = d->role == TRIBE_ROLE_OUT_PROJ || d->role == TRIBE_ROLE_FF2;
-  const bool bf_role = d->role == TRIBE_ROLE_QKV || d->role == TRIBE_ROLE_FF1;
-  if (!res_role && !bf_role) return false;
-  if (d->batch1 * d->batch0 != 1 || d->trans_ab || d->gather1 || d->N % 256 != 0 || d->rowadd || d->gadd || d->aux) return false;
-  if (d->c_dtype != (bf_role ? TRIBE_BF16 : TRIBE_F32) || d->ldc % 4 != 0 || ((uintptr_t)d->C % 16) != 0) return false;
-  const bool wants_bias = d->role == TRIBE_ROLE_FF1 || d->role == TRIBE_ROLE_FF2;
-  if (wants_bias ? (d->bias_mode != TRIBE_BIAS_COL || !d->bias || ((uintptr_t)d->bias % 16) != 0) : d->bias_mode != TRIBE_BIAS_NONE) return false;
-  if (d->act != (d->role == TRIBE_ROLE_FF1 ? TRIBE_ACT_GELU : TRIBE_ACT_NONE)) return false;
-  if (res_role) {
-    if (!d->res || d->ldres % 4 != 0 || ((uintptr_t)d->res % 16) != 0 || d->row_scale) return false;
-    if (d->res_scale && ((uintptr_t)d->res_scale % 16) != 0) return false;
-    if (d->c_bf16 && (d->ld_c_bf16 % 4 != 0 || ((uintptr_t)d->c_bf16 % 8) != 0)) return false;
-  } else {
-    if (d->res || d->res_scale || d->c_bf16 || d->row_sumsq) return false;
-  }
-  return (int64_t)255 * (d->lda > d->ldb ? d->lda : d->ldb) * 2 + 8192 < (1ll << 32);   // 32-bit per-lane offsets of the LDS-DMA pieces
-}
-// true when the descriptor carries exactly the operator set epilogue_role compiles for its role in the 8-wave NT kernel with tiles `bn` wide:
-// un-batched, alpha == 1, no tile crossing N, and every operand as aligned as epilogue_fast's vector accesses need (make_epi_ctx).
-// [row_scale] of QKV / FF1 and [res_scale], [c_bf16], [row_sumsq] of out-proj / FF2 may be absent (first layer, last layer, unfused norm).
-static bool role8_ok(const tribe_gemm_desc* d, int bn) {
-  const bool res_role = d->role == TRIBE_ROLE_OUT_PROJ || d->role == TRIBE_ROLE_FF2;
-  const bool bf_role = d->role == TRIBE_ROLE_QKV || d->role == TRIBE_ROLE_FF1;
-  if (!res_role && !bf_role) return false;
-  if (d->batch1 * d->batch0 != 1 || d->trans_ab || d->gather1 || d->N % bn != 0 || d->alpha != 1.0f || d->rowadd || d->gadd || d->aux) return false;
-  if (d->c_dtype != (bf_role ? TRIBE_BF16 : TRIBE_F32) || d->ldc % 4 != 0 || ((uintptr_t)d->C % (bf_role ? 8 : 16)) != 0) return false;
-  const bool wants_bias = d->role == TRIBE_ROLE_FF1 || d->role == TRIBE_ROLE_FF2;
-  if (wants_bias ? (d->bias_mode != TRIBE_BIAS_COL || !d->bias || ((uintptr_t)d->bias % 16) != 0) : d->bias_mode != TRIBE_BIAS_NONE) return false;
-  if (d->act != (d->role == TRIBE_ROLE_FF1 ? TRIBE_ACT_GELU : TRIBE_ACT_NONE)) return false;
-  if (res_role) {
-    if (!d->res || d->ldres % 4 != 0 || ((uintptr_t)d->res % 16) != 0 || d->row_scale) return false;
-    if (d->res_scale && ((uintptr_t)d->res_scale % 16) != 0) return false;
-    if (d->c_bf16 && (d->ld_c_bf16 % 4 != 0 || ((uintptr_t)d->c_bf16 % 8) != 0)) return false;
-  } else {
-    if (d->res || d->res_scale || d->c_bf16 || d->row_sumsq) return false;
-  }
-  return true;
-}
-static GemmPlan gemm_plan(const tribe_gemm_desc* d) {
-  const int64_t nz = d->batch1 * d->batch0;
-  auto tiles = [&](int64_t bm, int64_t bn) { return ((d->M + bm - 1) / bm) * ((d->N + bn - 1) / bn) * nz; };
-  const int64_t t256 = tiles(256, 256), t128 = tiles(128, 128);
-  const bool fused_norm = d->c_bf16 || d->row_sumsq || d->row_scale;
-  // 256^2 tiles when both extents fill them and the grid still covers the chip, else 128^2
-  int use_big = (d->M >= 256 && d->N >= 256 && t256 >= 96);
-  // Narrow, short-K products whose 256^2 grid is under two rounds of the 256 CUs (ViT-g attention projection: 8192 x 1408 x 1408 =
-  // 192 tiles) run faster on 128^2 tiles (60 -> 47 us; profiles/r02_o_gemm_shapes.txt); with K > 2048 or N > 2048 the 256^2 tiles'
-  // higher operand reuse wins back more than the idle CUs cost.
-  if (use_big && t256 < 512 && t128 >= 512 && d->K <= 2048 && d->N <= 2048) use_big = 0;
-  // 256-wide tiles that hang a quarter or more over the edge of a narrow C (dQ = dS K per head: N = 384 fills 1.5 of them) lose more MFMA
-  // work than 128^2 tiles cost: batched 1024 x 384 x 1024, 128 batches: 246 -> 204 us
-  if (use_big && t128 >= 512 && (double)t128 * 128 * 128 * 1.25 <= (double)t256 * 256 * 256) use_big = 0;
-  if (fused_norm && d->N % 128 != 0) use_big = 1;   // (the launcher then reports the N it needs)
-  if (d->tile_hint == 1 || d->tile_hint == 3) use_big = 0;
-  if (d->tile_hint == 2 || d->tile_hint == 4 || d->tile_hint == 5 || d->tile_hint == 6) use_big = 1;
-  if (d->trans_ab) return {KIND_BIG, 256, 256, 64};
-  if (!use_big) {
-    // one workgroup per CU or fewer: the ring kernel (three K-tiles in flight); more: the double-buffered kernel, whose two or three
-    // co-resident workgroups per CU cover for each other
-    const bool ring = d->tile_hint == 3 || (d->tile_hint != 1 && t128 <= 256 && d->K >= 256);
-    GemmPlan plan{ring ? KIND_RING : KIND_SMALL, 128, 128, 64};
-    // split-K (desc.stream_k): a grid of at most half a round whose tiles have K-steps to share out -- as many workgroups per tile as fit one
-    // round, at least 8 K-steps each, at most 8 shares; operators the second launch knows, 16-byte accessible operands
-    if (ring && d->stream_k && nz == 1 && !d->gather1 && !d->gadd && !d->aux && (d->act == TRIBE_ACT_NONE || d->act == TRIBE_ACT_GELU) &&
-        !(d->res && d->rowadd) && d->N % 4 == 0 && (!d->row_sumsq || d->N % 64 == 0) && d->ldc % 4 == 0 && ((uintptr_t)d->C % 16) == 0 &&
-        (d->bias_mode != TRIBE_BIAS_COL || ((uintptr_t)d->bias % 16) == 0) && (!d->res || (d->ldres % 4 == 0 && ((uintptr_t)d->res % 16) == 0)) &&
-        (!d->res_scale || ((uintptr_t)d->res_scale % 16) == 0) && (!d->rowadd || (d->ld_rowadd % 4 == 0 && ((uintptr_t)d->rowadd % 16) == 0)) &&
-        (!d->c_bf16 || (d->ld_c_bf16 % 4 == 0 && ((uintptr_t)d->c_bf16 % 8) == 0))) {
-      const int64_t nk = d->K / BK;
-      int64_t sp = 256 / t128;
-      if (sp > nk / 8) sp = nk / 8;
-      if (sp > 8) sp = 8;
-      if (sp >= 2) plan.splits = (int)sp;
-    }
-    return plan;
-  }
-  // Tile quantisation on 256 CUs: a grid of 256 x 192 tiles when that cuts the rounds' worth of work (BASELINE config at B = 4, M = 4096:
-  // QKV 576 -> 768 tiles = 3 rounds of 3/4-size tiles instead of 3 of full size; out-proj / FF2 192 -> 256 tiles: the whole chip
-  // instead of 3/4 of it).  A 192-wide tile costs ~0.78 of a 256-wide one; large grids keep 256^2 (higher operand reuse).
-  int bn = 256;
-  if (d->tile_hint == 4) bn = 192;
-  else if (d->tile_hint == 6) bn = (d->N % 256 != 0 && d->N % 192 == 0) ? 192 : 256;   // the width whose tiles stay inside N (A/B against the role kernels)
-  else if (d->tile_hint == 0 && d->N % 192 == 0 && t256 <= 2048) {
-    const int64_t t192 = tiles(256, 192);
-    const double cost4 = (double)((t256 + 255) / 256), cost3 = (double)((t192 + 255) / 256) * 0.78;
-    if (cost3 < 0.95 * cost4) bn = 192;
-  }
-  if (fused_norm && d->N % bn != 0) bn = (d->N % 256 == 0) ? 256 : 192;
-  // 256 x 256 tiles of the four encoder GEMMs: the one-wave-per-SIMD kernel, whose epilogue is compiled for exactly their operator sets
-  // (tile_hint 2 keeps the 8-wave form for A/B runs; everything else -- other roles, batched, transposed operands -- stays 8-wave)
-  // The one-wave-per-SIMD kernel (tile_hint 5; QKV / FF1 / out-proj / FF2 with their model epilogues).  History of the default: with the round-2
-  // epilogue in the 8-wave kernel it won QKV / FF1 by 4.4 / 4.5 % (profiles/r03_z1_4w_lab.txt); its epilogue techniques (transposed accumulation,
-  // paired 16-byte bf16 stores) then went into the 8-wave kernel (TACC), after which the two tie in isolation (profiles/r03_z2_4w_lab.txt) and in the
-  // whole step (same box, bench.py: 8-wave only 639.7 - 640.4 k TRs/s, 4-wave for QKV / FF1 637.2 - 638.2 k: the step runs at the chip's power
-  // limit, a kernel that draws less lets its neighbours clock higher and vice versa).  Default: 8-wave everywhere.
-  const bool w4_default = TRIBE_GEMM_4W_DEFAULT && d->tile_hint == 0 && (d->role == TRIBE_ROLE_QKV || d->role == TRIBE_ROLE_FF1);
-  if (bn == 256 && (d->tile_hint == 5 || w4_default) && w4_role_ok(d)) return {KIND_BIG4W, 256, 256, 64};
-  return {KIND_BIG, 256, bn, bn / 4};
-}
-// the 8-wave NT kernel with the role-compiled epilogue (tile_hint 6 = the same tiles with the generic epilogue, for A/B runs and tests).
-// Default per role by the same-box measurements of DESIGN 4.1b (B = 64, parent -> role kernel): QKV 2.774 -> 2.737 ms, FF1 3.881 -> 3.704 ms,
-// out-proj 1.212 -> 1.182 ms take it; FF2 (3.795 -> 3.782 ms, 3813 -> 3811 us in the kernel trace: inside the run-to-run spread -- its K = 12288
-// loop is 4x as long and its epilogue waits on the residual, not on instructions) keeps the generic epilogue unless tile_hint 2 / 4 asks.
-static bool takes_role_epilogue(const tribe_gemm_desc* d, const GemmPlan& plan) {
-  if (plan.kind != KIND_BIG || d->trans_ab || d->tile_hint == 6 || !role8_ok(d, plan.bn)) return false;
-  return d->role != TRIBE_ROLE_FF2 || d->tile_hint == 2 || d->tile_hint == 4;
-}
-}  // namespace tribe_gemm_detail
-
-namespace tribe_gemm_detail {
-// Stream-K plan of a launch with `tiles` output tiles of nk K-steps each (see SkSched): fills *sk and returns the grid size.  Whole rounds of
-// W tiles stay whole; the remainder is cut into W runs.  Not worth it (or not possible) -> the plain grid.
-unsigned plan_stream_k(int tiles, int nk, SkSched* sk) {
+// ---------------------------------------------------------------------------------------------
+// The C entry points.  What a launch will be is resolved once, on the host, by gemm_plan.cpp (checks, kernel, tile, symbol, grid, split,
+// workspace); the launch and the three queries below read that one GemmLaunch.
+// ---------------------------------------------------------------------------------------------
+namespace {
+// compute units of the current device, asked once per device (256 where there is no device to ask); both planners count rounds on it
+int device_cu_count() {
   static int cus[64] = {};
   int dev = 0;
   (void)hipGetDevice(&dev);
@@ -1501,158 +1367,36 @@ unsigned plan_stream_k(int tiles, int nk, SkSched* sk) {
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
     cus[dev] = n;
   }
-  const int W = cus[dev] < 256 ? cus[dev] : 256;
-  const int rem = tiles % W;
-  *sk = no_stream_k();
-  // Worth it only for remainders up to half a round.  Measured at B = 16 (profiles/r03_z12_gemm_streamk.txt, same numbers with atomics and
-  // with the workspace): remainder 64 of 256 (dW of FF1 / FF2: 576 tiles; the projectors: 64 tiles) 1284 -> 1076 us / 1294 -> 1086 us /
-  // 328 -> 161 us -- there a run is a clean quarter of a tile; remainder 176 (QKV) 848 -> 1007 us and 144 (out-proj) 334 -> 439 us: SLOWER --
-  // every run straddles two tiles at its own K offset, so the 32 workgroups of an XCD stop sharing operand panels in its L2 (the 4 x 8 patch
-  // of tile_coords) and the region turns memory-bound; and every part pays a prologue + epilogue (~45 us) for at most 1/2 tile of work.
-  // Also: runs of at least 8 K-steps.
-  if (rem == 0 || rem * 2 > W || (int64_t)rem * nk < (int64_t)W * 8) return (unsigned)tiles;
-  sk->tiles_dp = tiles - rem;
-  sk->rem_units = rem * nk;
-  sk->q = (sk->rem_units + W - 1) / W;
-  sk->workers = W;
-  // second parts, longest first
-  int len2[256], n2 = 0;
-  unsigned short who[256];
-  for (int w = 0; w < W; ++w) {
-    const int u0 = w * sk->q;
-    if (u0 >= sk->rem_units) break;
-    const int run = sk->q < sk->rem_units - u0 ? sk->q : sk->rem_units - u0;
-    const int x = u0 % nk, first = run < nk - x ? run : nk - x;
-    if (first < run) { len2[n2] = run - first; who[n2] = (unsigned short)w; ++n2; }
-  }
-  for (int i = 1; i < n2; ++i) {   // insertion sort, descending, stable
-    const int l = len2[i]; const unsigned short v = who[i];
-    int j = i - 1;
-    for (; j >= 0 && len2[j] < l; --j) { len2[j + 1] = len2[j]; who[j + 1] = who[j]; }
-    len2[j + 1] = l; who[j + 1] = v;
-  }
-  for (int i = 0; i < n2; ++i) sk->second_worker[i] = who[i];
-  return (unsigned)(sk->tiles_dp + W + n2);
+  return cus[dev];
 }
-}  // namespace tribe_gemm_detail
+}  // namespace
 
 extern "C" int tribe_gemm_bf16(const tribe_gemm_desc* d, void* stream) {
-  TRIBE_REQUIRE(d != nullptr, "tribe_gemm_bf16: null descriptor");
-  TRIBE_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "tribe_gemm_bf16: M, N, K must be positive (got %lld %lld %lld)",
-                (long long)d->M, (long long)d->N, (long long)d->K);
-  TRIBE_REQUIRE(d->K % BK == 0, "tribe_gemm_bf16: K=%lld must be a multiple of %d (zero-pad K)", (long long)d->K, BK);
-  TRIBE_REQUIRE(d->batch1 > 0 && d->batch0 > 0, "tribe_gemm_bf16: batch counts must be positive");
-  TRIBE_REQUIRE(d->A && d->B && d->C, "tribe_gemm_bf16: null operand");
-  TRIBE_REQUIRE(d->lda % 8 == 0 && d->ldb % 8 == 0 && d->sA1 % 8 == 0 && d->sA0 % 8 == 0 && d->sB1 % 8 == 0 &&
-                    d->sB0 % 8 == 0,
-                "tribe_gemm_bf16: lda/ldb/batch strides must be multiples of 8 elements (16-byte rows)");
-  TRIBE_REQUIRE(((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0, "tribe_gemm_bf16: A/B must be 16-byte aligned");
-  TRIBE_REQUIRE((d->trans_ab || (d->lda >= d->K && d->ldb >= d->K)) && d->ldc >= ((d->act == TRIBE_ACT_SWIGLU || d->act == TRIBE_ACT_GLU) ? d->N / 2 : d->N),
-                "tribe_gemm_bf16: leading dimension too small");
-  TRIBE_REQUIRE((d->act != TRIBE_ACT_SWIGLU && d->act != TRIBE_ACT_GLU) || (d->N % 2 == 0 && !d->res && !d->rowadd && !d->gadd && d->bias_mode != TRIBE_BIAS_ROW),
-                "tribe_gemm_bf16: SWIGLU needs an even N and no residual / row adds");
-  TRIBE_REQUIRE(d->c_dtype == TRIBE_F32 || d->c_dtype == TRIBE_BF16, "tribe_gemm_bf16: c_dtype must be f32 or bf16");
-  TRIBE_REQUIRE(d->bias_mode == TRIBE_BIAS_NONE || d->bias != nullptr, "tribe_gemm_bf16: bias_mode set without bias");
-  TRIBE_REQUIRE(!d->rowadd || d->rowadd_period > 0, "tribe_gemm_bf16: rowadd needs a positive period");
-  TRIBE_REQUIRE(!d->gadd || (d->gadd_index && d->gadd_div > 0), "tribe_gemm_bf16: gadd needs index and divisor");
-  TRIBE_REQUIRE(!(d->gather_a || d->gather_bias || d->gather_b) || d->gather1, "tribe_gemm_bf16: gather flags set without gather1");
-  TRIBE_REQUIRE(d->act != TRIBE_ACT_GELU_BWD || d->aux, "tribe_gemm_bf16: GELU_BWD needs the saved pre-activation in aux");
-  TRIBE_REQUIRE(d->act != TRIBE_ACT_MUL_AUX || (d->aux && d->ld_aux == d->ldc), "tribe_gemm_bf16: MUL_AUX needs aux laid out like C (ld_aux == ldc)");
-  TRIBE_REQUIRE((d->act != TRIBE_ACT_EXP2 && d->act != TRIBE_ACT_MUL_AUX) || (!d->res && !d->rowadd && !d->gadd && d->bias_mode != TRIBE_BIAS_COL),
-                "tribe_gemm_bf16: EXP2 / MUL_AUX take a row bias only");
-  // (aux is addressed with C's batch offsets: the GELU pre-activation is un-batched, MUL_AUX's factor shares C's layout)
-  TRIBE_REQUIRE(!d->aux || (d->ld_aux >= d->N && (d->batch1 * d->batch0 == 1 || d->act == TRIBE_ACT_MUL_AUX)),
-                "tribe_gemm_bf16: aux is supported for un-batched GEMMs (and for MUL_AUX)");
-  TRIBE_REQUIRE(d->sBias0 == 0 || d->bias_mode == TRIBE_BIAS_ROW, "tribe_gemm_bf16: sBias0 belongs to a row bias");
-  const int64_t nz = d->batch1 * d->batch0;
-  if (d->c_bf16 || d->row_sumsq || d->row_scale) {
-    // fused ScaleNorm operands exist only in the wait-free epilogue: insist on everything that path needs
-    TRIBE_REQUIRE(nz == 1 && !d->rowadd && !d->gadd && !d->aux && (d->act == TRIBE_ACT_NONE || d->act == TRIBE_ACT_GELU),
-                  "tribe_gemm_bf16: c_bf16 / row_sumsq / row_scale need an un-batched launch with plain operators");
-    TRIBE_REQUIRE(d->ldc % 4 == 0 && ((uintptr_t)d->C % 16) == 0 && (!d->bias || ((uintptr_t)d->bias % 16) == 0) &&
-                      (!d->res || (d->ldres % 4 == 0 && ((uintptr_t)d->res % 16) == 0)) && (!d->res_scale || ((uintptr_t)d->res_scale % 16) == 0),
-                  "tribe_gemm_bf16: c_bf16 / row_sumsq / row_scale need 16-byte aligned operands");
-    TRIBE_REQUIRE((!d->c_bf16 && !d->row_sumsq) || d->c_dtype == TRIBE_F32, "tribe_gemm_bf16: c_bf16 / row_sumsq accompany an f32 C");
-    TRIBE_REQUIRE(!d->c_bf16 || (d->ld_c_bf16 >= d->N && d->ld_c_bf16 % 4 == 0 && ((uintptr_t)d->c_bf16 % 8) == 0), "tribe_gemm_bf16: bad c_bf16");
-  }
-  const tribe_gemm_detail::GemmPlan plan = tribe_gemm_detail::gemm_plan(d);
-  if (d->c_bf16 || d->row_sumsq || d->row_scale) {
-    TRIBE_REQUIRE(d->N % plan.bn == 0, "tribe_gemm_bf16: c_bf16 / row_sumsq / row_scale need N (%lld) to be a multiple of the tile width %d",
-                  (long long)d->N, plan.bn);
-    TRIBE_REQUIRE(!d->row_sumsq || d->ld_row_sumsq >= d->N / plan.sumsq_cols, "tribe_gemm_bf16: ld_row_sumsq must cover N / %d slots (tribe_gemm_sumsq_slots)",
-                  plan.sumsq_cols);
-  }
-  if (d->trans_ab) {
-    TRIBE_REQUIRE(d->M >= 8 && d->N >= 8 && d->M % 8 == 0 && d->N % 8 == 0 && d->lda >= d->M && d->ldb >= d->N,
-                  "tribe_gemm_bf16: trans_ab takes At [K, M] and Bt [K, N] with M and N multiples of 8 and lda >= M, ldb >= N");
-    TRIBE_REQUIRE(!d->aux && d->act != TRIBE_ACT_SWIGLU && d->act != TRIBE_ACT_GLU && d->act != TRIBE_ACT_SILU && d->act != TRIBE_ACT_GELU_BWD &&
-                      d->act != TRIBE_ACT_EXP2 && d->act != TRIBE_ACT_MUL_AUX && !d->gather_a && !d->gather_b,
-                  "tribe_gemm_bf16: trans_ab supports the plain epilogue operators and no operand gather");
-  }
-  const int64_t tiles_m = (d->M + plan.bm - 1) / plan.bm, tiles_n = (d->N + plan.bn - 1) / plan.bn;
-  TRIBE_REQUIRE(tiles_m * tiles_n < (1ll << 31) && nz < 65536, "tribe_gemm_bf16: grid too large");
-
-  dim3 grid((unsigned)(tiles_m * tiles_n), (unsigned)nz, 1);
+  using namespace tribe_gemm_detail;
+  GemmLaunch p;
+  if (gemm_resolve(d, "tribe_gemm_bf16", device_cu_count(), &p) != 0 || gemm_check_workspace(d, "tribe_gemm_bf16", p) != 0) return -1;
+  // nothing below refuses the launch: a profile slot taken here always gets its stop event
   hipStream_t s = (hipStream_t)stream;
   const int role = (d->role >= 0 && d->role < TRIBE_ROLE_COUNT) ? d->role : TRIBE_ROLE_GENERIC;
-  const double flops = 2.0 * (double)d->M * (double)d->N * (double)d->K * (double)nz;
-  const int slot = prof_before(role, flops, s);
-  const bool bf = d->c_dtype == TRIBE_BF16;
-  if (d->trans_ab) {   // transposed operands: the 256^2 kernel only, plain epilogue operators
-    SkSched sk = tribe_gemm_detail::no_stream_k();
-    if (d->stream_k) {
-      TRIBE_REQUIRE(!bf && nz == 1 && d->bias_mode == TRIBE_BIAS_NONE && d->act == TRIBE_ACT_NONE && !d->res && !d->rowadd && !d->gadd,
-                    "tribe_gemm_bf16: stream_k takes a plain un-batched f32 product");
-      grid.x = tribe_gemm_detail::plan_stream_k((int)(tiles_m * tiles_n), (int)(d->K / BK), &sk);
-      if (sk.tiles_dp < tiles_m * tiles_n) {
-        const int64_t need = (int64_t)2 * sk.workers * SK_SLOT_FLOATS * 4;
-        TRIBE_REQUIRE(d->stream_k_ws && d->stream_k_ws_bytes >= need && ((uintptr_t)d->stream_k_ws % 16) == 0,
-                      "tribe_gemm_bf16: stream_k needs a 16-byte aligned workspace of %lld bytes (tribe_gemm_stream_k_workspace_bytes)", (long long)need);
-        sk.ws = (float*)d->stream_k_ws;
-      }
-    }
-    tribe_gemm_detail::launch_big4_tn(bf ? 1 : 0, grid, s, d, (int)tiles_m, (int)tiles_n, sk);
-    if (sk.tiles_dp < tiles_m * tiles_n)
-      hipLaunchKernelGGL(streamk_reduce_kernel, dim3((unsigned)(tiles_m * tiles_n - sk.tiles_dp)), dim3(512), 0, s, *d, (int)tiles_m, (int)tiles_n, sk);
-    prof_after(slot, s);
-    TRIBE_LAUNCH_CHECK();
-    return 0;
+  const int slot = prof_before(role, 2.0 * (double)d->M * (double)d->N * (double)d->K * (double)p.nz, s);
+  const dim3 grid(p.grid_x, (unsigned)p.nz, 1);
+  const int tiles_m = (int)p.tiles_m, tiles_n = (int)p.tiles_n, bf = d->c_dtype == TRIBE_BF16 ? 1 : 0;
+  switch (p.kind) {
+    case KIND_BIG4W: launch_4w(p.pair, grid, s, d, tiles_m, tiles_n); break;
+    case KIND_BIG:
+      if (d->trans_ab) {   // transposed operands: the 256^2 kernel only; a stream-K launch leaves the split tiles to the reduce kernel
+        const SkSched sk = kernel_arg(p.sk, d->stream_k_ws);
+        launch_big4_tn(bf, grid, s, d, tiles_m, tiles_n, sk);
+        if (p.reduce_grid_x) hipLaunchKernelGGL(streamk_reduce_kernel, dim3(p.reduce_grid_x), dim3(512), 0, s, *d, tiles_m, tiles_n, sk);
+      } else if (p.bn == 192) launch_big3(p.pair, grid, s, d, tiles_m, tiles_n);
+      else launch_big4(p.pair, grid, s, d, tiles_m, tiles_n);
+      break;
+    case KIND_RING:
+      launch_ring(p.pair, grid, s, d, tiles_m, tiles_n, p.splits, p.splits > 1 ? (float*)d->stream_k_ws : nullptr);
+      if (p.splits > 1) launch_splitk_epilogue(bf, s, d, p.splits, (const float*)d->stream_k_ws);
+      break;
+    default: launch_small(p.pair, grid, s, d, tiles_m, tiles_n); break;
   }
-  const bool ext = d->aux != nullptr || d->act == TRIBE_ACT_SWIGLU || d->act == TRIBE_ACT_GLU || d->act == TRIBE_ACT_SILU ||
-                   d->act == TRIBE_ACT_GELU_BWD || d->act == TRIBE_ACT_EXP2 || d->act == TRIBE_ACT_MUL_AUX;
-  int pair = bf ? 0 : 1;   // GENERIC
-  if (ext) {
-    pair = bf ? 2 : 3;
-  } else {
-    switch (role) {     // the (dtype, role) combinations the encode path launches have kernels of their own
-    case TRIBE_ROLE_PROJECTOR: if (!bf) pair = 4; break;
-    case TRIBE_ROLE_QKV: if (bf) pair = 5; break;
-    case TRIBE_ROLE_ATTN_SCORES: if (!bf) pair = 6; break;
-    case TRIBE_ROLE_ATTN_PV: if (bf) pair = 7; break;
-    case TRIBE_ROLE_OUT_PROJ: if (!bf) pair = 8; break;
-    case TRIBE_ROLE_FF1: if (bf) pair = 9; break;
-    case TRIBE_ROLE_FF2: if (!bf) pair = 10; break;
-    case TRIBE_ROLE_VOXEL_HEAD: if (!bf) pair = 11; break;
-    default: break;
-    }
-  }
-  using namespace tribe_gemm_detail;
-  // The 8-wave kernels of QKV / FF1 / out-proj / FF2 carry ONLY the epilogue of their role's operator set (epilogue_role): a launch of such a
-  // role with any other descriptor -- or with tile_hint 6, the A/B switch -- runs the generic epilogue under the GENERIC symbol.
-  if (plan.kind == KIND_BIG && (pair == 5 || pair == 8 || pair == 9 || pair == 10) && !takes_role_epilogue(d, plan)) pair = bf ? 0 : 1;
-  if (plan.kind == KIND_BIG4W) launch_4w(pair, grid, s, d, (int)tiles_m, (int)tiles_n);
-  else if (plan.kind == KIND_BIG && plan.bn == 192) launch_big3(pair, grid, s, d, (int)tiles_m, (int)tiles_n);
-  else if (plan.kind == KIND_BIG) launch_big4(pair, grid, s, d, (int)tiles_m, (int)tiles_n);
-  else if (plan.kind == KIND_RING && plan.splits > 1) {
-    const int64_t need = (int64_t)plan.splits * d->M * d->N * 4;
-    TRIBE_REQUIRE(d->stream_k_ws && d->stream_k_ws_bytes >= need && ((uintptr_t)d->stream_k_ws % 16) == 0,
-                  "tribe_gemm_bf16: this launch is split over K: stream_k_ws must hold %lld bytes (tribe_gemm_stream_k_workspace_bytes)", (long long)need);
-    TRIBE_REQUIRE(tiles_m * tiles_n * plan.splits < (1ll << 31) && d->M * (d->N / 4) < (1ll << 39), "tribe_gemm_bf16: grid too large");
-    grid.x = (unsigned)(tiles_m * tiles_n * plan.splits);
-    launch_ring(pair, grid, s, d, (int)tiles_m, (int)tiles_n, plan.splits, (float*)d->stream_k_ws);
-    launch_splitk_epilogue(bf ? 1 : 0, s, d, plan.splits, (const float*)d->stream_k_ws);
-  } else if (plan.kind == KIND_RING) launch_ring(pair, grid, s, d, (int)tiles_m, (int)tiles_n, 1, nullptr);
-  else launch_small(pair, grid, s, d, (int)tiles_m, (int)tiles_n);
   prof_after(slot, s);
   TRIBE_LAUNCH_CHECK();
   return 0;
@@ -1662,38 +1406,45 @@ extern "C" int tribe_gemm_bf16(const tribe_gemm_desc* d, void* stream) {
 // every tile is covered exactly once): out = {tiles_dp, rem_units, q, workers, second_worker[0 .. 255]}; returns the grid size
 extern "C" int tribe_gemm_stream_k_plan(int32_t tiles, int32_t nk, int32_t* out) {
   TRIBE_REQUIRE(tiles > 0 && nk > 0 && out != nullptr, "tribe_gemm_stream_k_plan: bad argument");
-  SkSched sk;
-  const unsigned grid = tribe_gemm_detail::plan_stream_k(tiles, nk, &sk);
+  SkSchedule sk;
+  const unsigned grid = tribe_gemm_detail::plan_stream_k(tiles, nk, device_cu_count(), &sk);
   out[0] = sk.tiles_dp; out[1] = sk.rem_units; out[2] = sk.q; out[3] = sk.workers;
   for (int i = 0; i < 256; ++i) out[4 + i] = sk.second_worker[i];
   return (int)grid;
 }
 
+// The three queries read the plan the launch will read.  Their checks are lax on purpose: callers size buffers with half-filled descriptors.
 extern "C" int64_t tribe_gemm_stream_k_workspace_bytes(const tribe_gemm_desc* d) {
   TRIBE_REQUIRE(d != nullptr && d->M > 0 && d->N > 0 && d->K > 0 && d->K % BK == 0, "tribe_gemm_stream_k_workspace_bytes: bad descriptor");
-  if (!d->stream_k || d->batch1 * d->batch0 != 1) return 0;
-  if (!d->trans_ab) {   // NT form: split-K of a small grid (ring kernel)
-    const tribe_gemm_detail::GemmPlan plan = tribe_gemm_detail::gemm_plan(d);
-    return plan.splits > 1 ? (int64_t)plan.splits * d->M * d->N * 4 : 0;
-  }
-  SkSched sk;
-  const int tiles = (int)(((d->M + 255) / 256) * ((d->N + 255) / 256));
-  if (tribe_gemm_detail::plan_stream_k(tiles, (int)(d->K / BK), &sk) == (unsigned)tiles) return 0;
-  return (int64_t)2 * sk.workers * SK_SLOT_FLOATS * 4;
+  return tribe_gemm_detail::gemm_plan(d, device_cu_count()).ws_need;   // 0 = not split -- also for a stream_k request whose operators the launch refuses
 }
 
 extern "C" int tribe_gemm_sumsq_slots(const tribe_gemm_desc* d) {
   TRIBE_REQUIRE(d != nullptr && d->M > 0 && d->N > 0 && d->K > 0 && d->batch1 > 0 && d->batch0 > 0, "tribe_gemm_sumsq_slots: bad descriptor");
-  const tribe_gemm_detail::GemmPlan plan = tribe_gemm_detail::gemm_plan(d);
-  return (int)(d->N / plan.sumsq_cols);
+  return (int)(d->N / tribe_gemm_detail::gemm_plan(d, device_cu_count()).sumsq_cols);
 }
 
 // which epilogue the launch of `desc` runs: 0 = the generic one (operators decided at run time), 1 = the 8-wave kernel's role-compiled one
 // (epilogue_role), 2 = the one-wave-per-SIMD kernel's (epilogue_w4).  Host-side only: no GPU call.
 extern "C" int tribe_gemm_epilogue_path(const tribe_gemm_desc* d) {
   TRIBE_REQUIRE(d != nullptr && d->M > 0 && d->N > 0 && d->K > 0 && d->batch1 > 0 && d->batch0 > 0, "tribe_gemm_epilogue_path: bad descriptor");
-  const tribe_gemm_detail::GemmPlan plan = tribe_gemm_detail::gemm_plan(d);
-  if (plan.kind == tribe_gemm_detail::KIND_BIG4W) return 2;
-  return tribe_gemm_detail::takes_role_epilogue(d, plan) ? 1 : 0;
+  return tribe_gemm_detail::gemm_plan(d, device_cu_count()).epilogue_path;
+}
+
+// Debug export (not in the header): what tribe_gemm_bf16 (fp8 = 0) or tribe_gemm_fp8 would launch for `d`, without launching it.
+// out = {return code, kind, bm, bn, sumsq_cols, splits, pair, epilogue_path, tiles_m, tiles_n, nz, grid_x, reduce_grid_x, sk.tiles_dp,
+// sk.rem_units, sk.q, sk.workers, second parts of the stream-K runs, ws_need}; all zero behind a non-zero return code (tribe_last_error).
+extern "C" int tribe_debug_gemm_plan(const tribe_gemm_desc* d, int32_t fp8, int64_t* out, int32_t n) {
+  using namespace tribe_gemm_detail;
+  TRIBE_REQUIRE(out != nullptr && n >= 19, "tribe_debug_gemm_plan: out must hold %d entries", 19);
+  GemmLaunch p{};
+  int rc = fp8 ? gemm_fp8_resolve(d, "tribe_gemm_fp8", &p) : gemm_resolve(d, "tribe_gemm_bf16", device_cu_count(), &p);
+  if (rc == 0 && !fp8) rc = gemm_check_workspace(d, "tribe_gemm_bf16", p);
+  if (rc != 0) p = GemmLaunch{};
+  const int64_t second = p.reduce_grid_x ? (int64_t)p.grid_x - p.sk.tiles_dp - p.sk.workers : 0;
+  const int64_t all[19] = {rc, p.kind, p.bm, p.bn, p.sumsq_cols, p.splits, p.pair, p.epilogue_path, p.tiles_m, p.tiles_n, p.nz, p.grid_x,
+                           p.reduce_grid_x, p.sk.tiles_dp, p.sk.rem_units, p.sk.q, p.sk.workers, second, p.ws_need};
+  for (int i = 0; i < 19; ++i) out[i] = all[i];
+  return rc;
 }
 #endif  // part 0

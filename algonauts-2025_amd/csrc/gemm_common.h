@@ -643,3 +643,19 @@ __device__ __forceinline__ void epilogue_tile16(const tribe_gemm_desc& g, const 
     epilogue_row4<OUT_BF16, EXT>(g, c, v, mt0 + ((lane >> 4) << 2) + (lane & 3), nt0 + (((lane & 15) >> 2) << 2));
   }
 }
+
+// Host side: one launch of a tile kernel KERNEL(desc, tiles_m, tiles_n, extra...) with SMEM bytes of dynamic LDS.  The dynamic-LDS
+// attribute is set once per kernel AND device (one process may drive several GPUs).
+namespace tribe_gemm_detail {
+template <auto KERNEL, int THREADS, int SMEM, class... Extra>
+static void launch_k(dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n, const Extra&... extra) {
+  static bool attr_done[64] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+    if (dev >= 0 && dev < 64) attr_done[dev] = true;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS, 1, 1), SMEM, s, *d, tiles_m, tiles_n, extra...);
+}
+}  // namespace tribe_gemm_detail

@@ -10,6 +10,7 @@
 // 16-byte LDS chunks 2*(lane>>4) and 2*(lane>>4)+1 (any k-permutation shared by A and B is valid for the instruction;
 // measured with ab_tmp probe in round 1).  Roofline: MFMA (dense fp8, 5 PFLOP/s).
 #include "gemm_common.h"
+#include "gemm_plan.h"
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 typedef __attribute__((ext_vector_type(4))) int i32x4_t;
@@ -244,45 +245,18 @@ __global__ __launch_bounds__(256) void absmax_kernel(const T* __restrict__ x, in
 }  // namespace
 
 extern "C" int tribe_gemm_fp8(const tribe_gemm_desc* d, void* stream) {
-  TRIBE_REQUIRE(d != nullptr, "tribe_gemm_fp8: null descriptor");
-  TRIBE_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "tribe_gemm_fp8: M, N, K must be positive (got %lld %lld %lld)", (long long)d->M,
-                (long long)d->N, (long long)d->K);
-  TRIBE_REQUIRE(d->K % 128 == 0, "tribe_gemm_fp8: K=%lld must be a multiple of 128 (zero-pad K)", (long long)d->K);
-  TRIBE_REQUIRE(d->batch1 > 0 && d->batch0 > 0, "tribe_gemm_fp8: batch counts must be positive");
-  TRIBE_REQUIRE(d->A && d->B && d->C, "tribe_gemm_fp8: null operand");
-  TRIBE_REQUIRE(d->lda % 16 == 0 && d->ldb % 16 == 0 && d->sA1 % 16 == 0 && d->sA0 % 16 == 0 && d->sB1 % 16 == 0 && d->sB0 % 16 == 0,
-                "tribe_gemm_fp8: lda/ldb/batch strides must be multiples of 16 elements (16-byte rows)");
-  TRIBE_REQUIRE(((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0, "tribe_gemm_fp8: A/B must be 16-byte aligned");
-  TRIBE_REQUIRE(d->lda >= d->K && d->ldb >= d->K && d->ldc >= ((d->act == TRIBE_ACT_SWIGLU || d->act == TRIBE_ACT_GLU) ? d->N / 2 : d->N),
-                "tribe_gemm_fp8: leading dimension too small");
-  TRIBE_REQUIRE((d->act != TRIBE_ACT_SWIGLU && d->act != TRIBE_ACT_GLU) || (d->N % 2 == 0 && !d->res && !d->rowadd && !d->gadd && d->bias_mode != TRIBE_BIAS_ROW),
-                "tribe_gemm_fp8: SWIGLU / GLU need an even N and no residual / row adds");
-  TRIBE_REQUIRE(d->c_dtype == TRIBE_F32 || d->c_dtype == TRIBE_BF16, "tribe_gemm_fp8: c_dtype must be f32 or bf16");
-  TRIBE_REQUIRE(d->bias_mode == TRIBE_BIAS_NONE || d->bias != nullptr, "tribe_gemm_fp8: bias_mode set without bias");
-  TRIBE_REQUIRE(!d->rowadd || d->rowadd_period > 0, "tribe_gemm_fp8: rowadd needs a positive period");
-  TRIBE_REQUIRE(!d->gadd || (d->gadd_index && d->gadd_div > 0), "tribe_gemm_fp8: gadd needs index and divisor");
-  TRIBE_REQUIRE(!(d->gather_a || d->gather_bias || d->gather_b) || d->gather1, "tribe_gemm_fp8: gather flags set without gather1");
-  TRIBE_REQUIRE(d->act != TRIBE_ACT_GELU_BWD && !d->aux, "tribe_gemm_fp8: the training-only epilogues (aux, GELU_BWD) are bf16-only");
-  const int64_t nz = d->batch1 * d->batch0;
-  const int64_t tiles_m = (d->M + big::BM - 1) / big::BM, tiles_n = (d->N + big::BN - 1) / big::BN;
-  TRIBE_REQUIRE(tiles_m * tiles_n < (1ll << 31) && nz < 65536, "tribe_gemm_fp8: grid too large");
-  dim3 grid((unsigned)(tiles_m * tiles_n), (unsigned)nz, 1);
+  using namespace tribe_gemm_detail;
+  GemmLaunch p;   // the descriptor checks shared with tribe_gemm_bf16, the fp8-only ones and the grid: gemm_plan.cpp
+  if (gemm_fp8_resolve(d, "tribe_gemm_fp8", &p) != 0) return -1;
+  const dim3 grid(p.grid_x, (unsigned)p.nz, 1);
   hipStream_t s = (hipStream_t)stream;
-#define TRIBE_FP8_LAUNCH(BF, EXT)                                                                                            \
-  do {                                                                                                                       \
-    static bool attr_done = false;                                                                                           \
-    if (!attr_done) {                                                                                                        \
-      (void)hipFuncSetAttribute((const void*)gemm_fp8_nt_256x256x128<BF, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                big::SMEM_BYTES);                                                                            \
-      attr_done = true;                                                                                                      \
-    }                                                                                                                        \
-    hipLaunchKernelGGL((gemm_fp8_nt_256x256x128<BF, EXT>), grid, dim3(512, 1, 1), big::SMEM_BYTES, s, *d, (int)tiles_m, (int)tiles_n); \
-  } while (0)
-  const bool bf = d->c_dtype == TRIBE_BF16;
-  const bool ext = d->act == TRIBE_ACT_SWIGLU || d->act == TRIBE_ACT_GLU || d->act == TRIBE_ACT_SILU;
-  if (ext) { if (bf) TRIBE_FP8_LAUNCH(1, 1); else TRIBE_FP8_LAUNCH(0, 1); }
-  else { if (bf) TRIBE_FP8_LAUNCH(1, 0); else TRIBE_FP8_LAUNCH(0, 0); }
-#undef TRIBE_FP8_LAUNCH
+  const int tiles_m = (int)p.tiles_m, tiles_n = (int)p.tiles_n;
+  switch (p.pair) {   // <output is bf16, extended epilogue (SwiGLU / GLU / SiLU)>
+    case PAIR_EXT_BF16: launch_k<gemm_fp8_nt_256x256x128<1, 1>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
+    case PAIR_EXT_F32: launch_k<gemm_fp8_nt_256x256x128<0, 1>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
+    case PAIR_GENERIC_BF16: launch_k<gemm_fp8_nt_256x256x128<1, 0>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
+    default: launch_k<gemm_fp8_nt_256x256x128<0, 0>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n); break;
+  }
   TRIBE_LAUNCH_CHECK();
   return 0;
 }

@@ -54,8 +54,9 @@ def grad_sums_and_cast(dy: torch.Tensor, M: int, N: int, res: torch.Tensor | Non
     return sa, sab, bf
 
 
-# weight gradients through the stream-K schedule of the transposed-operand GEMM (tribe_gemm_desc.stream_k): dW of a 3072 x 3072 layer is 144
-# tiles on 256 CUs, of a 12288 x 3072 one 576 = 2.25 rounds.  Split tiles are summed in a fixed order: bit-reproducible.
+# weight gradients may take the stream-K schedule of the transposed-operand GEMM (tribe_gemm_desc.stream_k).  The planner cuts only a last
+# round that is at most half full: dW of a 12288 x 3072 layer (576 tiles = 2.25 rounds of 256 CUs) and of the 64-tile projectors are split,
+# dW of a 3072 x 3072 layer (144 tiles) and of QKV (432) stay whole.  Split tiles are summed in a fixed order: bit-reproducible.
 STREAM_K_WGRAD = True
 
 

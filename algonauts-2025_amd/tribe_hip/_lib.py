@@ -308,6 +308,7 @@ SIGNATURES = {
 # exports that are not part of include/tribe_hip.h: hooks that let the tests reach an internal entry point
 DEBUG_SIGNATURES = {
     "tribe_debug_attention_qrot": (C.c_int, [vp, i64, i64, i32, i32, f32, vp, vp, vp, i32, vp]),
+    "tribe_debug_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), i32, C.POINTER(i64), i32]),
 }
 
 _lib = None

@@ -117,8 +117,10 @@ typedef struct tribe_gemm_desc {
   int64_t sBias0;          /* + b0 * sBias0 on the bias pointer (a ROW bias per (b1, b0) batch: the attention backward's -lse2 / -scale * D); 0 = none */
   /* 1 = the launcher may share out the REDUCTION of a launch whose output tiles do not fill the chip over more workgroups; the parts travel
    * through stream_k_ws and a second launch on the same stream sums them in a fixed order (bit-reproducible) and writes C.
-   *   trans_ab (the weight-gradient form: dW of a 3072 x 3072 layer is 144 tiles on 256 CUs): stream-K -- the tiles of the last, partial round
-   *     are cut into equal runs of K-steps over all CUs.  Plain f32 product only (no bias / activation / residual / batch).
+   *   trans_ab (the weight-gradient form): stream-K -- the tiles of the last, partial round are cut into equal runs of K-steps over all CUs,
+   *     when that round is at most HALF full and a run gets at least 8 K-steps: dW of a 12288 x 3072 layer (576 tiles = 2 rounds + 64 on 256 CUs)
+   *     and of the 64-tile projectors are split; dW of a 3072 x 3072 layer (144 tiles) is not -- fuller remainders measured slower split.
+   *     Plain f32 product only (no bias / activation / residual / batch): the launch refuses anything else.
    *   otherwise (NT form): split-K of grids of at most half a round of 128 x 128 tiles (M = 128 rows: BASELINE config 1) -- 2..8 workgroups
    *     per tile; the second launch applies alpha, row_scale, bias, GELU, the scaled residual or periodic row add, c_bf16 and row_sumsq.
    * The workspace must hold tribe_gemm_stream_k_workspace_bytes(desc) bytes (0 = this launch is not split), 16-byte aligned, and is free
@@ -135,7 +137,8 @@ int tribe_gemm_sumsq_slots(const tribe_gemm_desc* desc);
  * kernel's epilogue compiled for the operator set of desc->role (QKV / FF1 / OUT_PROJ / FF2 with exactly their model operators, un-batched,
  * alpha == 1, N a multiple of the tile width, 16-byte operands; FF2 only under tile_hint 2 / 4), 2 = the one-wave-per-SIMD kernel's (tile_hint 5); < 0 on a bad descriptor */
 int tribe_gemm_epilogue_path(const tribe_gemm_desc* desc);
-/* bytes of desc->stream_k_ws this launch needs: 0 when it would not be split (stream_k clear, not trans_ab, or no partial round worth cutting) */
+/* bytes of desc->stream_k_ws this launch needs, read from the plan the launch itself reads: 0 when it would not be split (stream_k clear, no
+ * partial round or small grid worth cutting, or a trans_ab request with operators the launch refuses) */
 int64_t tribe_gemm_stream_k_workspace_bytes(const tribe_gemm_desc* desc);
 /* The stream-K schedule of a launch with `tiles` output tiles of `nk` K-steps on this device (host-only, for inspection and tests):
  * out[0..3] = {tiles computed whole, K-steps in the split region, K-steps per run, runs}, out[4 .. 259] = the order in which the runs' second

@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")/../algonauts-2025_amd/csrc"
 mkdir -p ../../ab_tmp
 FL="-O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wno-unused-function"
-build() { /opt/rocm/bin/hipcc $FL $2 -c gemm.hip -o ../../ab_tmp/gemm_abl_$1.o && /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 ../../ab_tmp/gemm_abl_$1.o abi.o -o ../../ab_tmp/libgemm_abl_$1.so; }
+build() { /opt/rocm/bin/hipcc $FL $2 -c gemm.hip -o ../../ab_tmp/gemm_abl_$1.o && /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 ../../ab_tmp/gemm_abl_$1.o gemm_plan.o abi.o -o ../../ab_tmp/libgemm_abl_$1.so; }
 build base "" &
 build nolds "-DTRIBE_ABL_NO_LDSREAD" &
 build nostage "-DTRIBE_ABL_NO_STAGE" &

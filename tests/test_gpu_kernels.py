@@ -560,6 +560,24 @@ def test_gemm_transposed_operands_stream_k(ops, M, N, K, splits):
         ops.gemm_tn(at, bt, stream_k=True, bias=_dev(torch.zeros(N)))
 
 
+def test_refused_gemm_launch_takes_no_profile_slot(ops):
+    """A launch the resolve step refuses returns before prof_before: the in-library event profile holds the launches that ran and nothing
+    else.  (A slot taken for a refused launch never got its stop event, and tribe_prof_end then lost the profile of the whole run.)"""
+    g = torch.Generator().manual_seed(7)
+    at, bt = _dev(torch.randn(512, 256, generator=g)).bfloat16(), _dev(torch.randn(512, 256, generator=g)).bfloat16()
+    a, b = _dev(torch.randn(128, 64, generator=g)).bfloat16(), _dev(torch.randn(128, 64, generator=g)).bfloat16()
+    bias = _dev(torch.zeros(256))
+    ops.prof_begin(16)
+    try:
+        with pytest.raises(ValueError, match="stream_k takes a plain un-batched f32 product"):
+            ops.gemm_tn(at, bt, stream_k=True, bias=bias)
+        out = ops.gemm_nt(a, b)
+    finally:
+        prof = ops.prof_end()
+    assert sum(r["launches"] for r in prof.values()) == 1 and prof["generic"]["launches"] == 1
+    torch.testing.assert_close(out, a.float() @ b.float().t(), rtol=1e-4, atol=1e-3)
+
+
 # dim_head 64 (the extractors) on the 64-row-per-wave kernels (mode 4: four waves; mode 5: anti-phase wave pairs; mode 0 picks by
 # grid size) and on the 16-row kernel (mode 2): several query blocks, ragged last key tile and last row tile, one sub-tile only
 # (T = 20), an odd number of sub-tiles (T = 1000: 32 sub-tiles, T = 3000: 94, T = 257: 9), a late deferred-max rescale.
