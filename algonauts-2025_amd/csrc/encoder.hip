@@ -25,6 +25,21 @@ extern "C" int tribe_attention_set_mode(int32_t mode) {
   return 0;
 }
 
+// The residual stream between the first out-proj and the last FF2 as two 16-bit planes (enum tribe_c_planes) instead of f32 + bf16 copy:
+// one third fewer bytes written by the 2 * depth - 2 middle residual epilogues.  Process-wide, like g_attn_mode.
+static int g_res_planes = 1;
+static int g_res_tile_hint = 0;   // tile_hint of the out-proj / FF2 launches (2: the 256 x 256 role kernel at any shape, for tests and A/B runs)
+extern "C" int tribe_encoder_set_residual_planes(int32_t on) {
+  TRIBE_REQUIRE(on == 0 || on == 1, "tribe_encoder_set_residual_planes: 0 (f32 stream + bf16 copy) or 1 (16-bit hi / lo planes where the kernels allow)");
+  g_res_planes = on;
+  return 0;
+}
+extern "C" int tribe_encoder_set_residual_tile_hint(int32_t hint) {
+  TRIBE_REQUIRE(hint == 0 || hint == 2, "tribe_encoder_set_residual_tile_hint: 0 (automatic) or 2 (256 x 256 role kernel)");
+  g_res_tile_hint = hint;
+  return 0;
+}
+
 namespace {
 
 // attention is processed in batch chunks so that the f32 score block stays near the Infinity Cache size
@@ -202,6 +217,32 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
   // final one (its consumer, the voxel head, has x on the column side) stay stand-alone launches: 2 instead of 2 * depth + 1.
   const bool fuse = p.fuse_norm;
   bool have_factors = false;   // rowf / xn describe the current x
+  // The two GEMMs of layer l that write the residual stream (ff2 = false: out-proj), ld_row_sumsq left to the caller.  as_planes: between the
+  // first out-proj (f32 x in) and the last FF2 (f32 x out) the stream is the pair (hi = xn, lo = half the bytes of x), read and written in place.
+  auto residual_gemm = [&](int l, bool ff2, bool as_planes) {
+    const tribe_encoder_layer& L = d->layers_host[l];
+    const bool first = l == 0 && !ff2, last = l + 1 == d->depth && ff2;
+    tribe_gemm_desc g = ff2 ? Linear(TRIBE_ROLE_FF2, M, hbuf, d->ff_inner, L.w_ff2, L.b_ff2, x, dim, TRIBE_F32).residual(x)
+                            : Linear(TRIBE_ROLE_OUT_PROJ, M, ao, inner, L.w_out, nullptr, x, dim, TRIBE_F32).residual(x);
+    g.res_scale = ff2 ? L.ff_res_scale : L.attn_res_scale;
+    g.tile_hint = g_res_tile_hint;
+    if (fuse && !last) { g.c_bf16 = xn; g.ld_c_bf16 = dim; g.row_sumsq = ssq; }
+    if (as_planes) {   // lo lives in x itself: the first 128 bytes of every 64-column strip's 256 (rows 2 dim 16-bit slots apart), in place
+      g.c_dtype = first ? TRIBE_F32_PLANES_OUT : (last ? TRIBE_F32_PLANES_IN : TRIBE_F32_PLANES_INOUT);
+      g.c_bf16 = xn; g.ld_c_bf16 = dim;
+      if (!first) g.ldres = 2 * dim;
+      if (!last) g.ldc = 2 * dim;
+    }
+    return g;
+  };
+  // planes: only where every residual launch of the forward runs the 256 x 256 role kernel (else the path is the f32 one throughout)
+  bool planes = g_res_planes && fuse && p.split_bytes == 0 && d->depth > 0;
+  for (int l = 0; planes && l < d->depth; ++l) {
+    for (int ff2 = 0; planes && ff2 < 2; ++ff2) {
+      const tribe_gemm_desc g = residual_gemm(l, ff2 != 0, true);
+      planes = tribe_gemm_epilogue_path(&g) == 1;
+    }
+  }
 
   for (int l = 0; l < d->depth; ++l) {
     const tribe_encoder_layer& L = d->layers_host[l];
@@ -231,10 +272,8 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
                                                          d->rot_dim, (hipStream_t)stream)
                    : tribe_attention_fwd(qkv, d->B, d->T, d->heads, d->dim_head, scale, ao, p.attn_ws, p.attn_bytes, stream);
     if (rc) return rc;
-    g = Linear(TRIBE_ROLE_OUT_PROJ, M, ao, inner, L.w_out, nullptr, x, dim, TRIBE_F32).residual(x);
-    g.res_scale = L.attn_res_scale;
+    g = residual_gemm(l, false, planes);
     if (fuse) {
-      g.c_bf16 = xn; g.ld_c_bf16 = dim; g.row_sumsq = ssq;
       n_part = tribe_gemm_sumsq_slots(&g);
       TRIBE_REQUIRE(n_part > 0 && n_part <= dim / 32, "tribe_encoder_fwd: unexpected row_sumsq slot count %lld", (long long)n_part);
       g.ld_row_sumsq = n_part;
@@ -251,11 +290,9 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
     allow_split(g);
     rc = tribe_gemm_bf16(&g, stream);
     if (rc) return rc;
-    g = Linear(TRIBE_ROLE_FF2, M, hbuf, d->ff_inner, L.w_ff2, L.b_ff2, x, dim, TRIBE_F32).residual(x);
-    g.res_scale = L.ff_res_scale;
+    g = residual_gemm(l, true, planes);
     have_factors = fuse && l + 1 < d->depth;   // the next layer's QKV takes the raw bf16(x) + factors
     if (have_factors) {
-      g.c_bf16 = xn; g.ld_c_bf16 = dim; g.row_sumsq = ssq;
       n_part = tribe_gemm_sumsq_slots(&g);
       TRIBE_REQUIRE(n_part > 0 && n_part <= dim / 32, "tribe_encoder_fwd: unexpected row_sumsq slot count %lld", (long long)n_part);
       g.ld_row_sumsq = n_part;

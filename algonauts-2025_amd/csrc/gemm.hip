@@ -87,9 +87,11 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // The fields live in SkSchedule (gemm_plan.h), which the host planner fills; this is the kernels' parameter type.
 struct SkSched : SkSchedule {};
 
-template <int OUT_BF16, int ROLE, int TN = 0, int NB = 4>
+// PL (out-proj / FF2 at NB = 4 only): the residual stream as two 16-bit planes, see epilogue_role.
+template <int OUT_BF16, int ROLE, int TN = 0, int NB = 4, int PL = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt_256x256x64(const tribe_gemm_desc g, int tiles_m, int tiles_n, const SkSched sk) {
   static_assert(NB >= 2 && NB <= 4 && (!TN || NB == 4), "tile columns: 128, 192 or 256; transposed operands: 256 only");
+  static_assert(PL == 0 || (!TN && NB == 4 && !OUT_BF16 && (ROLE == TRIBE_ROLE_OUT_PROJ || ROLE == TRIBE_ROLE_FF2)), "planes: out-proj / FF2, 256 x 256");
   constexpr int BM = big::BM, BN = 64 * NB, A_BYTES = big::A_BYTES, BUF_BYTES = A_BYTES + BN * BK * 2;
   constexpr int WN = 16 * NB;                      // columns per wave
   constexpr int VM_STEADY = NB == 4 ? TRIBE_GEMM_VM_STEADY : 4 + NB;
@@ -420,7 +422,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_256x256x64(const tribe_gemm_de
   // launch of such a role runs under the GENERIC symbol.
   constexpr bool ROLE_EPI = TACC && (ROLE == TRIBE_ROLE_QKV || ROLE == TRIBE_ROLE_FF1 || ROLE == TRIBE_ROLE_OUT_PROJ || ROLE == TRIBE_ROLE_FF2);
   if constexpr (ROLE_EPI) {
-    epilogue_role<OUT_BF16, ROLE, 8, NB, TACC>(g, acc, m0 + wr * 128, n0 + wc * WN, lane, smem + wave * (4 * NB * 1024));
+    epilogue_role<OUT_BF16, ROLE, 8, NB, TACC, PL>(g, acc, m0 + wr * 128, n0 + wc * WN, lane, smem + wave * (4 * NB * 1024));
   } else if (epilogue_fast_ok<(ROLE == TRIBE_ROLE_EXT)>(g, ctx) && n0 + BN <= g.N) {
     // nothing inside the sub-tile loop waits on memory (gemm_common.h); the staging buffers are idle by now
     epilogue_fast<OUT_BF16, 8, NB, (ROLE == TRIBE_ROLE_EXT), TACC>(g, ctx, acc, m0 + wr * 128, n0 + wc * WN, lane, smem + wave * (4 * NB * 1024));
@@ -1179,6 +1181,7 @@ __global__ __launch_bounds__(256, 1) void gemm_nt_4w256(const tribe_gemm_desc g,
 namespace tribe_gemm_detail {
 void launch_big4(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n);
 void launch_big4_tn(int bf, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n, const SkSched& sk);
+void launch_big4_planes(dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n);
 void launch_big3(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n);
 void launch_ring(int pair, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n, int splits, float* ws);
 void launch_splitk_epilogue(int bf, hipStream_t s, const tribe_gemm_desc* d, int splits, const float* ws);
@@ -1203,6 +1206,20 @@ inline SkSched kernel_arg(const SkSchedule& plan, void* ws = nullptr) {
 #define TRIBE_GEMM_CASE_launch_big4(idx, bf, role) \
   case idx: launch_k<gemm_nt_256x256x64<bf, role, 0, 4>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, kernel_arg(no_stream_k())); break;
 TRIBE_GEMM_TABLE(launch_big4)
+// the plane forms of the two residual roles (desc.c_dtype = an enum tribe_c_planes value; gemm_resolve lets nothing else through)
+template <int ROLE>
+static void launch_planes_of(dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n) {
+  const SkSched sk = kernel_arg(no_stream_k());
+  switch (d->c_dtype) {
+    case TRIBE_F32_PLANES_OUT: launch_k<gemm_nt_256x256x64<0, ROLE, 0, 4, 1>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, sk); break;
+    case TRIBE_F32_PLANES_INOUT: launch_k<gemm_nt_256x256x64<0, ROLE, 0, 4, 2>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, sk); break;
+    default: launch_k<gemm_nt_256x256x64<0, ROLE, 0, 4, 3>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, sk); break;
+  }
+}
+void launch_big4_planes(dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n) {
+  if (d->role == TRIBE_ROLE_OUT_PROJ) launch_planes_of<TRIBE_ROLE_OUT_PROJ>(grid, s, d, tiles_m, tiles_n);
+  else launch_planes_of<TRIBE_ROLE_FF2>(grid, s, d, tiles_m, tiles_n);
+}
 void launch_big4_tn(int bf, dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n, const SkSched& sk) {
   if (bf) launch_k<gemm_nt_256x256x64<1, TRIBE_ROLE_GENERIC, 1, 4>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, sk);
   else launch_k<gemm_nt_256x256x64<0, TRIBE_ROLE_GENERIC, 1, 4>, 512, big::SMEM_BYTES>(grid, s, d, tiles_m, tiles_n, sk);
@@ -1350,9 +1367,38 @@ extern "C" int tribe_rownorm_scale_fwd(const float* partial, int64_t rows, int64
   return 0;
 }
 
+// The plane format of the residual epilogues (gemm_common.h: f32_to_plane_lo / planes_to_f32) element by element: tests and debugging.
+namespace {
+__global__ __launch_bounds__(256) void f32_to_planes_kernel(const float* __restrict__ x, int64_t n, unsigned short* __restrict__ hi,
+                                                            unsigned short* __restrict__ lo) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const float v = x[i];
+    hi[i] = f32_to_bf16(v);
+    lo[i] = (unsigned short)f32_to_plane_lo(v);
+  }
+}
+__global__ __launch_bounds__(256) void planes_to_f32_kernel(const unsigned short* __restrict__ hi, const unsigned short* __restrict__ lo, int64_t n,
+                                                            float* __restrict__ x) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] = planes_to_f32(hi[i], lo[i]);
+}
+}  // namespace
+
+extern "C" int tribe_f32_to_planes(const float* x, int64_t n, uint16_t* hi, uint16_t* lo, void* stream) {
+  TRIBE_REQUIRE(x && hi && lo && n > 0, "tribe_f32_to_planes: bad argument");
+  hipLaunchKernelGGL(f32_to_planes_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, n, hi, lo);
+  TRIBE_LAUNCH_CHECK();
+  return 0;
+}
+extern "C" int tribe_planes_to_f32(const uint16_t* hi, const uint16_t* lo, int64_t n, float* x, void* stream) {
+  TRIBE_REQUIRE(x && hi && lo && n > 0, "tribe_planes_to_f32: bad argument");
+  hipLaunchKernelGGL(planes_to_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, hi, lo, n, x);
+  TRIBE_LAUNCH_CHECK();
+  return 0;
+}
+
 
 // ---------------------------------------------------------------------------------------------
-// The C entry points.  What a launch will be is resolved once, on the host, by gemm_plan.cpp (checks, kernel, tile, symbol, grid, split,
+// The C entry points. What a launch will be is resolved once, on the host, by gemm_plan.cpp (checks, kernel, tile, symbol, grid, split,
 // workspace); the launch and the three queries below read that one GemmLaunch.
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -1389,6 +1435,7 @@ extern "C" int tribe_gemm_bf16(const tribe_gemm_desc* d, void* stream) {
         launch_big4_tn(bf, grid, s, d, tiles_m, tiles_n, sk);
         if (p.reduce_grid_x) hipLaunchKernelGGL(streamk_reduce_kernel, dim3(p.reduce_grid_x), dim3(512), 0, s, *d, tiles_m, tiles_n, sk);
       } else if (p.bn == 192) launch_big3(p.pair, grid, s, d, tiles_m, tiles_n);
+      else if (d->c_dtype >= TRIBE_F32_PLANES_OUT) launch_big4_planes(grid, s, d, tiles_m, tiles_n);
       else launch_big4(p.pair, grid, s, d, tiles_m, tiles_n);
       break;
     case KIND_RING:

@@ -497,6 +497,40 @@ __device__ __forceinline__ float mul_unfused(float a, float b) {
   return a * b;
 }
 
+// The f32 residual stream as two 16-bit planes (enum tribe_c_planes): hi = RNE bf16(v) -- what the next GEMM reads as its A operand anyway --
+// and lo = the low half of the f32 word.  RNE rounded the top half up exactly when lo > 0x8000, or lo == 0x8000 under an odd top half;
+// the decoder takes "up" for lo > 0x8000 only, so the one tie that rounded up is stored as lo = 0x8001 (the element then carries
+// v + 1 ulp; hi stays).  The subtraction runs on the whole bit pattern, so a carry into the exponent (or into Inf) undoes itself; a NaN
+// keeps a non-zero significand either way and +-Inf (lo == 0) comes back as it is.
+__device__ __forceinline__ unsigned int f32_to_plane_lo(float v) {
+  const unsigned int w = __float_as_uint(v);
+  return (w & 0x1ffffu) == 0x18000u ? 0x8001u : (w & 0xffffu);
+}
+__device__ __forceinline__ float planes_to_f32(unsigned int hi, unsigned int lo) {   // both in the low 16 bits
+  return __uint_as_float(((hi - (lo > 0x8000u ? 1u : 0u)) << 16) | lo);
+}
+// The same for the two elements of a packed pair, as the epilogues hold them:
+//   decode: ((hi - (lo > 0x8000)) << 16) | lo == (hi << 16) + sext16(lo - 1) + 1 modulo 2^32 -- lo - 1 is negative as a 16-bit number exactly for
+//           lo > 0x8000 (then it takes the 0x10000 off) and for lo == 0 (then - 1 + 1 == 0); one packed 16-bit subtraction serves both halves;
+//   encode: the tie-up adds 1 to a low half that is 0x8000, so nothing carries into the upper half.
+typedef unsigned short tribe_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void planes_to_f32x2(unsigned int hi2, unsigned int lo2, float& r0, float& r1) {
+  const tribe_u16x2 a = __builtin_bit_cast(tribe_u16x2, lo2) - (tribe_u16x2)(1);
+  r0 = __uint_as_float((hi2 << 16) + (unsigned int)(int)(short)a.x + 1u);
+  r1 = __uint_as_float((hi2 & 0xffff0000u) + (unsigned int)(int)(short)a.y + 1u);
+}
+__device__ __forceinline__ unsigned int f32x2_to_plane_lo(float v0, float v1) {
+  const unsigned int w0 = __float_as_uint(v0), w1 = __float_as_uint(v1);
+  const unsigned int t0 = (w0 & 0x1ffffu) == 0x18000u ? 1u : 0u, t1 = (w1 & 0x1ffffu) == 0x18000u ? 1u : 0u;
+  return ((w0 + t0) & 0xffffu) | ((w1 + t1) << 16);
+}
+
+// v0^2 + v1^2 + v2^2 + v3^2 with every product rounded on its own and the sums in that order: what the f32 epilogues' row_sumsq term
+// compiles to (packed multiplies, then adds), pinned for the plane variants so that their slots stay bit-equal to the f32 mode's
+__device__ __forceinline__ float sumsq4(const float (&v)[4]) {
+  return ((mul_unfused(v[0], v[0]) + mul_unfused(v[1], v[1])) + mul_unfused(v[2], v[2])) + mul_unfused(v[3], v[3]);
+}
+
 // epilogue_fast<.., TACC = 1> with the operator set of one encoder GEMM fixed at COMPILE time (the 8-wave NT kernel; the launcher's
 // role8_ok sends a descriptor here only when it carries exactly this set, un-batched, alpha == 1, tiles inside N, 16-byte operands):
 //   QKV       [row_scale] -> bf16                              FF1   [row_scale] + column bias + gelu_poly2 -> bf16
@@ -505,7 +539,15 @@ __device__ __forceinline__ float mul_unfused(float a, float b) {
 // floating-point operations per element -- outputs are bit-identical to epilogue_fast's -- but no test of an operator the role lacks,
 // no multiplication by alpha, and every store address is a per-lane row pointer stepped by 16 rows (the column offset of sub-tile j is an
 // immediate) instead of a 64-bit c_off + row * ldc + col rebuilt per store.  23 (QKV) to 63 (FF1) instructions per sub-tile.
-template <int OUT_BF16, int ROLE, int NI, int NJ, int TACC>
+// PL (out-proj / FF2, NJ = 4): the residual stream as two 16-bit planes (desc.c_dtype, enum tribe_c_planes): 0 = f32 in, f32 + bf16 copy out;
+// 1 = f32 in, planes out; 2 = planes in and out (in place); 3 = planes in, f32 out.  hi lives in c_bf16, lo in res (in) / C (out), strip by strip
+// in the first half of the bytes the f32 words would take (below).
+//   fetch: one 16-byte LDS-DMA request per lane covers 8 consecutive 16-bit columns -- lane f brings row f & 15, columns 8 (f >> 4) .. + 7 of a
+//          PAIR of sub-tiles (32 columns) -- so a round of 16 sub-tiles is 8 hi + 8 lo requests (the same 16), and a lane reads its 4 columns of
+//          sub-tile j back with one 8-byte LDS read per plane;
+//   store: lo is paired exactly like hi (two v_permlane32_swap, one 16-byte store per sub-tile pair), in place of the f32 store.
+// Same floating-point operations in the same order on the decoded residual; row_sumsq from the f32 value before the split.
+template <int OUT_BF16, int ROLE, int NI, int NJ, int TACC, int PL = 0>
 __device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t (&acc)[NI][NJ], int64_t mw, int64_t nw, int lane, char* lds_wave) {
   constexpr bool BIAS = ROLE == TRIBE_ROLE_FF1 || ROLE == TRIBE_ROLE_FF2;
   constexpr bool GELU = ROLE == TRIBE_ROLE_FF1;
@@ -513,6 +555,8 @@ __device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t 
   constexpr int RI = 4, ROUNDS = NI / RI;
   static_assert(TACC == 1 && NI % RI == 0 && NJ >= 1 && NJ <= 4, "transposed accumulators, rounds of 4 sub-tile rows");
   static_assert(OUT_BF16 == (RES ? 0 : 1), "QKV / FF1 write bf16, out-proj / FF2 the f32 residual stream");
+  static_assert(PL == 0 || (RES && NJ == 4 && PL >= 1 && PL <= 3), "planes: the residual roles at 256-column tiles");
+  constexpr bool PL_IN = PL == 2 || PL == 3, PL_OUT = PL == 1 || PL == 2;
   const int tq = lane >> 4;
   const int64_t row0 = mw + (lane & 15);                                   // + 16 i
   const int64_t col0 = nw + 4 * ((tq & 1) * 2 + (tq >> 1));                // + 16 j
@@ -520,7 +564,7 @@ __device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t 
   const int64_t left = g.M - row0;
   const int rows_left = left >= 16 * NI ? 16 * NI : (left > 0 ? (int)left : 0);   // sub-tile row i of this lane is inside M iff 16 i < rows_left
   const bool has_rs = !RES && g.row_scale != nullptr, has_rsc = RES && g.res_scale != nullptr;
-  const bool has_cb = RES && g.c_bf16 != nullptr, has_ssq = RES && g.row_sumsq != nullptr;
+  const bool has_cb = PL_OUT || (PL == 0 && RES && g.c_bf16 != nullptr), has_ssq = RES && g.row_sumsq != nullptr;
   float4 bcol[NJ], rsc[NJ];
   static_for<NJ>([&](auto jt) {
     constexpr int j = decltype(jt)::value;
@@ -530,8 +574,18 @@ __device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t 
   // row pointers of sub-tile row 0, advanced by 16 rows after every sub-tile row
   unsigned short* c16 = OUT_BF16 ? (unsigned short*)g.C + row0 * g.ldc : (has_cb ? g.c_bf16 + row0 * g.ld_c_bf16 : nullptr);   // the bf16 rows
   const int64_t step16 = 16 * (OUT_BF16 ? g.ldc : g.ld_c_bf16);
-  float* c32 = RES ? (float*)g.C + row0 * g.ldc + col0 : nullptr;
-  const float* rsrc = RES ? g.res + row0 * g.ldres + col0 : nullptr;
+  float* c32 = (RES && !PL_OUT) ? (float*)g.C + row0 * g.ldc + col0 : nullptr;
+  const float* rsrc = (RES && !PL_IN) ? g.res + row0 * g.ldres + col0 : nullptr;
+  // The lo plane is laid out so that it can live INSIDE the f32 buffer it replaces: column c of a row sits at 16-bit index
+  // 2 (c & ~63) + (c & 63) -- the first 128 bytes of the 256 bytes that the f32 words of this wave's 64-column strip occupy (one whole
+  // 128-byte line of every two; rows 2 N apart).  A wave then reads and writes nothing outside its own strip in either format, so the
+  // f32 -> planes and planes -> f32 launches run in place on the caller's x exactly like the f32 epilogue does (a round's fetches are
+  // retired before its stores), and the stream needs no buffer of its own.  (nw is a multiple of 64: the strip begins at 2 nw.)
+  unsigned short* clo = PL_OUT ? (unsigned short*)g.C + row0 * g.ldc + nw : nullptr;                                 // the lo rows written (+ colp)
+  const unsigned short* hsrc = PL_IN ? g.c_bf16 + row0 * g.ld_c_bf16 + nw + 8 * tq : nullptr;                        // + 32 per sub-tile pair
+  const unsigned short* lsrc = PL_IN ? (const unsigned short*)g.res + row0 * g.ldres + 2 * nw + 8 * tq : nullptr;
+  // where this lane's 4 columns of sub-tile j sit in the 1 KiB a pair's request left in LDS: chunk (j & 1) * 2 + (tq & 1), upper half for tq >= 2
+  const int pl_rd = (tq & 1) * 256 + (lane & 15) * 16 + (tq >> 1) * 8;
   static_for<ROUNDS>([&](auto rt) {
     constexpr int round = decltype(rt)::value;
     float srow[RI], ssq[RI];
@@ -540,7 +594,7 @@ __device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t 
       ssq[i4] = 0.f;
       srow[i4] = (has_rs && i * 16 < rows_left) ? g.row_scale[row0 + i * 16] : 1.0f;
     });
-    if constexpr (RES) {
+    if constexpr (RES && !PL_IN) {
       static_for<RI>([&](auto it) {
         constexpr int i4 = decltype(it)::value, i = round * RI + i4;
         if (i * 16 < rows_left) {   // rows past M (bottom tile row): the lane neither fetches nor stores
@@ -553,7 +607,23 @@ __device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t 
       });
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the DMA's LDS writes are invisible to the compiler's own counters
     }
+    if constexpr (PL_IN) {   // hi planes of the round's 8 sub-tile pairs in the first 8 KiB, lo planes in the second
+      static_for<RI>([&](auto it) {
+        constexpr int i4 = decltype(it)::value, i = round * RI + i4;
+        if (i * 16 < rows_left) {
+          static_for<NJ / 2>([&](auto pt) {
+            constexpr int jp = decltype(pt)::value;
+            __builtin_amdgcn_global_load_lds((gptr_t)(hsrc + jp * 32), (lptr_t)(lds_wave + (i4 * 2 + jp) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)(lsrc + jp * 32), (lptr_t)(lds_wave + 8192 + (i4 * 2 + jp) * 1024), 16, 0, 0);
+          });
+        }
+        hsrc += 16 * g.ld_c_bf16;
+        lsrc += 16 * g.ldres;
+      });
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     uint2 pend = make_uint2(0u, 0u);   // the packed bf16 quad of a pair's first sub-tile
+    uint2 pend_lo = make_uint2(0u, 0u);   // planes: the same for the lo plane
     static_for<RI * NJ>([&](auto st) {
       constexpr int s = decltype(st)::value, i4 = s / NJ, i = round * RI + i4, j = s % NJ;
       const bool live = i * 16 < rows_left;   // (every lane stays for the half-wave exchanges of the paired stores; loads and stores are guarded)
@@ -567,9 +637,19 @@ __device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t 
         const f32x2_t lo = gelu_poly2(f32x2_t{v[0], v[1]}), hi = gelu_poly2(f32x2_t{v[2], v[3]});
         v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
       }
-      if constexpr (RES) {
+      if constexpr (RES && !PL_IN) {
         const float4 r = *(const float4*)(lds_wave + s * 1024 + lane * 16);
         v[0] += r.x * rsc[j].x; v[1] += r.y * rsc[j].y; v[2] += r.z * rsc[j].z; v[3] += r.w * rsc[j].w;
+      }
+      if constexpr (PL_IN) {
+        const char* slot = lds_wave + (i4 * 2 + (j >> 1)) * 1024 + (j & 1) * 512 + pl_rd;
+        const uint2 h = *(const uint2*)slot, l = *(const uint2*)(slot + 8192);
+        float r0, r1, r2, r3;
+        planes_to_f32x2(h.x, l.x, r0, r1);
+        planes_to_f32x2(h.y, l.y, r2, r3);
+        // the f32 form above compiles to fused multiply-adds; said outright here, where the compiler sees other operands
+        v[0] = __builtin_fmaf(r0, rsc[j].x, v[0]); v[1] = __builtin_fmaf(r1, rsc[j].y, v[1]);
+        v[2] = __builtin_fmaf(r2, rsc[j].z, v[2]); v[3] = __builtin_fmaf(r3, rsc[j].w, v[3]);
       }
       // a bf16 row of 4 values: alone (8 bytes), or -- sub-tiles in pairs -- merged with the partner half-wave's into 16 bytes
       auto store_bf16 = [&]() {
@@ -592,14 +672,30 @@ __device__ __forceinline__ void epilogue_role(const tribe_gemm_desc& g, f32x4_t 
       };
       if constexpr (OUT_BF16) {
         store_bf16();
+      } else if constexpr (PL_OUT) {
+        store_bf16();   // the hi plane: the next GEMM's A operand, as ever
+        const uint2 pk = make_uint2(f32x2_to_plane_lo(v[0], v[1]), f32x2_to_plane_lo(v[2], v[3]));
+        if constexpr ((j & 1) == 0) {
+          pend_lo = pk;
+        } else {
+          const auto sx = __builtin_amdgcn_permlane32_swap(pend_lo.x, pk.x, false, false);
+          const auto sy = __builtin_amdgcn_permlane32_swap(pend_lo.y, pk.y, false, false);
+          if (live) *(uint4*)(clo + colp + (j - 1) * 16) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+        }
+        if (has_ssq && live) ssq[i4] += sumsq4(v);
       } else {
         if (live) *(float4*)(c32 + j * 16) = make_float4(v[0], v[1], v[2], v[3]);
         if (has_cb) store_bf16();   // the next GEMM's A operand, un-normalised (its ScaleNorm factor rides in that GEMM's row_scale)
-        if (has_ssq && live) ssq[i4] += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+        if constexpr (PL != 0) {
+          if (has_ssq && live) ssq[i4] += sumsq4(v);
+        } else {
+          if (has_ssq && live) ssq[i4] += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
+        }
       }
       if constexpr (j == NJ - 1) {   // next sub-tile row
         c16 += step16;
-        if constexpr (RES) c32 += 16 * g.ldc;
+        if constexpr (RES && !PL_OUT) c32 += 16 * g.ldc;
+        if constexpr (PL_OUT) clo += 16 * g.ldc;
       }
     });
     if constexpr (RES) {

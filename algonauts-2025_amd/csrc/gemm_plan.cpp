@@ -19,6 +19,8 @@ namespace {
 bool aligned(const void* p, unsigned bytes) { return ((uintptr_t)p % bytes) == 0; }
 bool is_fused_norm(const tribe_gemm_desc* d) { return d->c_bf16 || d->row_sumsq || d->row_scale; }
 bool is_gated(const tribe_gemm_desc* d) { return d->act == TRIBE_ACT_SWIGLU || d->act == TRIBE_ACT_GLU; }
+// the residual stream as two 16-bit planes (enum tribe_c_planes): hi in c_bf16, lo in res (in) / C (out)
+bool is_planes(const tribe_gemm_desc* d) { return d->c_dtype >= TRIBE_F32_PLANES_OUT && d->c_dtype <= TRIBE_F32_PLANES_IN; }
 
 // true when the descriptor carries exactly the operator set a role-compiled epilogue holds, un-batched, no tile of width `bn` crossing N,
 // and every operand as aligned as its vector accesses need.  [row_scale] of QKV / FF1 and [res_scale], [c_bf16], [row_sumsq] of
@@ -31,7 +33,13 @@ bool role_operators_ok(const tribe_gemm_desc* d, int bn, bool alpha_must_be_1, u
   if (!res_role && !bf_role) return false;
   if (d->batch1 * d->batch0 != 1 || d->trans_ab || d->gather1 || d->N % bn != 0 || (alpha_must_be_1 && d->alpha != 1.0f) || d->rowadd || d->gadd || d->aux)
     return false;
-  if (d->c_dtype != (bf_role ? TRIBE_BF16 : TRIBE_F32) || d->ldc % 4 != 0 || !aligned(d->C, bf_role ? bf16_c_align : 16)) return false;
+  const bool planes = res_role && is_planes(d);
+  if (!planes && d->c_dtype != (bf_role ? TRIBE_BF16 : TRIBE_F32)) return false;
+  if (d->ldc % 4 != 0 || !aligned(d->C, bf_role ? bf16_c_align : 16)) return false;
+  // planes: 8 columns per 16-byte request / paired store in each plane, and a hi plane to read or write
+  if (planes && (d->ldc % 8 != 0 || d->ldres % 8 != 0 || !d->c_bf16 || d->ld_c_bf16 % 8 != 0 || !aligned(d->c_bf16, 16))) return false;
+  // a lo row is 2 N 16-bit slots wide (the first half of every 64-column strip's f32 bytes: it can live in the f32 buffer itself)
+  if (planes && ((d->c_dtype != TRIBE_F32_PLANES_IN && d->ldc < 2 * d->N) || (d->c_dtype != TRIBE_F32_PLANES_OUT && d->ldres < 2 * d->N))) return false;
   const bool wants_bias = d->role == TRIBE_ROLE_FF1 || d->role == TRIBE_ROLE_FF2;
   if (wants_bias ? (d->bias_mode != TRIBE_BIAS_COL || !d->bias || !aligned(d->bias, 16)) : d->bias_mode != TRIBE_BIAS_NONE) return false;
   if (d->act != (d->role == TRIBE_ROLE_FF1 ? TRIBE_ACT_GELU : TRIBE_ACT_NONE)) return false;
@@ -126,6 +134,7 @@ void plan_tiles(const tribe_gemm_desc* d, int cu_count, GemmLaunch* p) {
 // loop is 4x as long and its epilogue waits on the residual, not on instructions) keeps the generic epilogue unless tile_hint 2 / 4 asks.
 bool takes_role_epilogue(const tribe_gemm_desc* d, const GemmLaunch& p) {
   if (p.kind != KIND_BIG || d->trans_ab || d->tile_hint == 6 || !role8_ok(d, p.bn)) return false;
+  if (is_planes(d)) return p.bn == 256;   // the plane epilogues exist in the 256 x 256 role kernels only, FF2's included
   return d->role != TRIBE_ROLE_FF2 || d->tile_hint == 2 || d->tile_hint == 4;
 }
 // The kernel symbol: the (dtype, role) combinations the encode path launches have kernels of their own.
@@ -222,7 +231,7 @@ static int check_operands(const tribe_gemm_desc* d, const char* who, bool fp8) {
   REQUIRE(((!fp8 && d->trans_ab) || (d->lda >= d->K && d->ldb >= d->K)) && d->ldc >= (is_gated(d) ? d->N / 2 : d->N), "leading dimension too small");
   REQUIRE(!is_gated(d) || (d->N % 2 == 0 && !d->res && !d->rowadd && !d->gadd && d->bias_mode != TRIBE_BIAS_ROW),
           "%s an even N and no residual / row adds", fp8 ? "SWIGLU / GLU need" : "SWIGLU needs");
-  REQUIRE(d->c_dtype == TRIBE_F32 || d->c_dtype == TRIBE_BF16, "c_dtype must be f32 or bf16");
+  REQUIRE(d->c_dtype == TRIBE_F32 || d->c_dtype == TRIBE_BF16 || (!fp8 && is_planes(d)), "c_dtype must be f32 or bf16");
   REQUIRE(d->bias_mode == TRIBE_BIAS_NONE || d->bias != nullptr, "bias_mode set without bias");
   REQUIRE(!d->rowadd || d->rowadd_period > 0, "rowadd needs a positive period");
   REQUIRE(!d->gadd || (d->gadd_index && d->gadd_div > 0), "gadd needs index and divisor");
@@ -248,10 +257,13 @@ int gemm_resolve(const tribe_gemm_desc* d, const char* who, int cu_count, GemmLa
     REQUIRE(d->ldc % 4 == 0 && aligned(d->C, 16) && (!d->bias || aligned(d->bias, 16)) && (!d->res || (d->ldres % 4 == 0 && aligned(d->res, 16))) &&
                 (!d->res_scale || aligned(d->res_scale, 16)),
             "c_bf16 / row_sumsq / row_scale need 16-byte aligned operands");
-    REQUIRE((!d->c_bf16 && !d->row_sumsq) || d->c_dtype == TRIBE_F32, "c_bf16 / row_sumsq accompany an f32 C");
+    REQUIRE((!d->c_bf16 && !d->row_sumsq) || d->c_dtype == TRIBE_F32 || is_planes(d), "c_bf16 / row_sumsq accompany an f32 C");
     REQUIRE(!d->c_bf16 || (d->ld_c_bf16 >= d->N && d->ld_c_bf16 % 4 == 0 && aligned(d->c_bf16, 8)), "bad c_bf16");
   }
   *p = gemm_plan(d, cu_count);
+  // (split-K plans are KIND_RING, transposed operands never take the role epilogue)
+  REQUIRE(!is_planes(d) || (p->kind == KIND_BIG && p->bn == 256 && p->epilogue_path == 1),
+          "the plane c_dtype values (16-bit hi / lo residual stream) run on the out-proj / FF2 role kernels at 256 x 256 tiles only");
   if (is_fused_norm(d)) {
     REQUIRE(d->N % p->bn == 0, "c_bf16 / row_sumsq / row_scale need N (%lld) to be a multiple of the tile width %d", (long long)d->N, p->bn);
     REQUIRE(!d->row_sumsq || d->ld_row_sumsq >= d->N / p->sumsq_cols, "ld_row_sumsq must cover N / %d slots (tribe_gemm_sumsq_slots)", p->sumsq_cols);

@@ -17,6 +17,7 @@ _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libtribe_hip.so"
 
 F32, BF16, F64 = 0, 1, 2
+F32_PLANES_OUT, F32_PLANES_INOUT, F32_PLANES_IN = 16, 17, 18   # enum tribe_c_planes (tribe_gemm_desc.c_dtype of the residual role kernels)
 ACT_NONE, ACT_GELU, ACT_SWIGLU, ACT_SILU, ACT_GLU, ACT_GELU_BWD, ACT_EXP2, ACT_MUL_AUX = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_RELU, ACT_ELU = 8, 9   # tribe_norm_act_fwd / tribe_norm_act_bwd only
 BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2
@@ -195,6 +196,8 @@ SIGNATURES = {
     "tribe_gemm_bf16": (C.c_int, [C.POINTER(GemmDesc), vp]),
     "tribe_gemm_sumsq_slots": (C.c_int, [C.POINTER(GemmDesc)]),
     "tribe_gemm_epilogue_path": (C.c_int, [C.POINTER(GemmDesc)]),
+    "tribe_f32_to_planes": (C.c_int, [vp, i64, vp, vp, vp]),
+    "tribe_planes_to_f32": (C.c_int, [vp, vp, i64, vp, vp]),
     "tribe_gemm_stream_k_workspace_bytes": (i64, [C.POINTER(GemmDesc)]),
     "tribe_gemm_stream_k_plan": (C.c_int, [i32, i32, C.POINTER(i32)]),
     "tribe_prof_begin": (C.c_int, [i32]),
@@ -271,6 +274,8 @@ SIGNATURES = {
     "tribe_attention_lse_supported": (C.c_int, [i32, i32]),
     "tribe_attention_set_mode": (C.c_int, [i32]),
     "tribe_attention_fwd": (C.c_int, [vp, i64, i64, i32, i32, f32, vp, vp, sz, vp]),
+    "tribe_encoder_set_residual_planes": (C.c_int, [i32]),
+    "tribe_encoder_set_residual_tile_hint": (C.c_int, [i32]),
     "tribe_encoder_workspace_bytes": (sz, [C.POINTER(EncoderDesc)]),
     "tribe_encoder_fwd": (C.c_int, [C.POINTER(EncoderDesc), vp, vp, i32, vp, sz, vp]),
     "tribe_voxel_head_fwd": (C.c_int, [vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp]),

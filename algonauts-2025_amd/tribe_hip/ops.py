@@ -540,6 +540,36 @@ def attention_set_mode(mode: int) -> None:
     check(lib().tribe_attention_set_mode(mode), "tribe_attention_set_mode")
 
 
+def encoder_set_residual_planes(on: bool) -> None:
+    """True (default): encoder_fwd keeps the residual stream between its first out-proj and last FF2 as 16-bit hi / lo planes where the
+    kernels allow; False: f32 stream + bf16 copy.  Process-wide."""
+    check(lib().tribe_encoder_set_residual_planes(int(on)), "tribe_encoder_set_residual_planes")
+
+
+def encoder_set_residual_tile_hint(hint: int) -> None:
+    """tile_hint of encoder_fwd's out-proj / FF2 launches: 0 (default) or 2 (256 x 256 role kernel at any shape; tests, A/B runs)."""
+    check(lib().tribe_encoder_set_residual_tile_hint(hint), "tribe_encoder_set_residual_tile_hint")
+
+
+def f32_to_planes(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """f32 -> (hi, lo) int16 planes of the residual role kernels' stream format (hi = the bf16 bits); debugging and tests."""
+    _cuda(x, torch.float32, "x")
+    x = x.contiguous()
+    hi, lo = torch.empty(x.shape, dtype=torch.int16, device=x.device), torch.empty(x.shape, dtype=torch.int16, device=x.device)
+    check(lib().tribe_f32_to_planes(x.data_ptr(), x.numel(), hi.data_ptr(), lo.data_ptr(), _stream()), "tribe_f32_to_planes")
+    return hi, lo
+
+
+def planes_to_f32(hi: torch.Tensor, lo: torch.Tensor) -> torch.Tensor:
+    _cuda(hi, torch.int16, "hi")
+    _cuda(lo, torch.int16, "lo")
+    if hi.shape != lo.shape or not hi.is_contiguous() or not lo.is_contiguous():
+        raise ValueError("planes_to_f32: hi and lo must be contiguous and of one shape")
+    x = torch.empty(hi.shape, dtype=torch.float32, device=hi.device)
+    check(lib().tribe_planes_to_f32(hi.data_ptr(), lo.data_ptr(), hi.numel(), x.data_ptr(), _stream()), "tribe_planes_to_f32")
+    return x
+
+
 def attention(qkv: torch.Tensor, B: int, T: int, heads: int, dim_head: int, scale: float) -> torch.Tensor:
     _cuda(qkv, torch.bfloat16, "qkv")
     if qkv.numel() != B * T * 3 * heads * dim_head:

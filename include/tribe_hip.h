@@ -33,6 +33,18 @@ extern "C" {
 #define TRIBE_ABI_VERSION 5   /* bumped whenever a descriptor struct changes layout (round 2 changed three without a bump) */
 
 enum tribe_dtype { TRIBE_F32 = 0, TRIBE_BF16 = 1, TRIBE_F64 = 2 };
+/* tribe_gemm_desc.c_dtype only: the f32 residual stream kept as TWO 16-bit planes, hi = bf16(x) rounded to nearest even (what c_bf16
+ * holds anyway: the next GEMM's A operand) and lo = the low 16 bits of the f32 word, so that the stream is written once instead of as
+ * f32 + bf16 copy.  Decode: word = ((hi - (lo > 0x8000)) << 16) | lo.  Lossless except for the exact tie that rounded UP (lo == 0x8000
+ * under an odd top half), which is stored as lo = 0x8001: that element carries x + 1 ulp.  hi is never altered.
+ * A lo row is 2 N 16-bit slots wide: column c sits at slot 2 (c & ~63) + (c & 63), i.e. in the first 128 bytes of the 256 that the f32 words
+ * of its 64-column strip take.  The plane can therefore live INSIDE the f32 buffer it stands for (lo pointer = the f32 pointer, pitch 2 * ld):
+ * every launch below then runs in place on that buffer, as the f32 epilogue does, and the stream needs no memory of its own.
+ * Out-proj / FF2 role kernels at 256 x 256 tiles only (tribe_gemm_epilogue_path == 1); every other launch refuses these values.
+ *   PLANES_OUT    res = f32 [M, ldres];                c_bf16 = hi out, C = lo out (ldc >= 2 N 16-bit slots; may be res itself)
+ *   PLANES_INOUT  hi in = c_bf16, lo in = res (ldres >= 2 N slots, may alias C);   c_bf16 = hi out (in place), C = lo out
+ *   PLANES_IN     hi in = c_bf16 (read only), lo in = res (ldres >= 2 N slots);    C = f32 out (may be res itself), no bf16 copy */
+enum tribe_c_planes { TRIBE_F32_PLANES_OUT = 16, TRIBE_F32_PLANES_INOUT = 17, TRIBE_F32_PLANES_IN = 18 };
 enum tribe_act {
   TRIBE_ACT_NONE = 0,
   TRIBE_ACT_GELU = 1,   /* exact (erf) GELU */
@@ -84,7 +96,7 @@ typedef struct tribe_gemm_desc {
   const void* A; int64_t lda, sA1, sA0;
   const void* B; int64_t ldb, sB1, sB0;
   void* C; int64_t ldc, sC1, sC0;
-  int32_t c_dtype;         /* TRIBE_F32 or TRIBE_BF16 */
+  int32_t c_dtype;         /* TRIBE_F32 or TRIBE_BF16 (or an enum tribe_c_planes value: the residual stream as two 16-bit planes) */
   float alpha;
   const int64_t* gather1;  /* optional [batch1]: index replacing b1 for A (gather_a) and bias (gather_bias) */
   int32_t gather_a, gather_bias;
@@ -135,8 +147,12 @@ int tribe_gemm_bf16(const tribe_gemm_desc* desc, void* stream);
 int tribe_gemm_sumsq_slots(const tribe_gemm_desc* desc);
 /* which epilogue the launch of `desc` runs (host-side, no GPU call): 0 = generic (operators decided at run time), 1 = the 8-wave 256-row
  * kernel's epilogue compiled for the operator set of desc->role (QKV / FF1 / OUT_PROJ / FF2 with exactly their model operators, un-batched,
- * alpha == 1, N a multiple of the tile width, 16-byte operands; FF2 only under tile_hint 2 / 4), 2 = the one-wave-per-SIMD kernel's (tile_hint 5); < 0 on a bad descriptor */
+ * alpha == 1, N a multiple of the tile width, 16-byte operands; FF2 only under tile_hint 2 / 4 or with a tribe_c_planes c_dtype, which reports 1
+ * at 256 x 256 tiles only), 2 = the one-wave-per-SIMD kernel's (tile_hint 5); < 0 on a bad descriptor */
 int tribe_gemm_epilogue_path(const tribe_gemm_desc* desc);
+/* The plane format of enum tribe_c_planes as stand-alone kernels (tests, debugging; not on the hot path): n f32 words -> hi, lo and back. */
+int tribe_f32_to_planes(const float* x, int64_t n, uint16_t* hi, uint16_t* lo, void* stream);
+int tribe_planes_to_f32(const uint16_t* hi, const uint16_t* lo, int64_t n, float* x, void* stream);
 /* bytes of desc->stream_k_ws this launch needs, read from the plan the launch itself reads: 0 when it would not be split (stream_k clear, no
  * partial round or small grid worth cutting, or a trans_ab request with operators the launch refuses) */
 int64_t tribe_gemm_stream_k_workspace_bytes(const tribe_gemm_desc* desc);
@@ -272,6 +288,14 @@ typedef struct tribe_encoder_desc {
   const float* cos_tab; const float* sin_tab; /* f32 [T, rot_dim/2] or NULL when rot_dim == 0 */
 } tribe_encoder_desc;
 
+/* Process-wide switches beside tribe_attention_set_mode (set them from one thread, between launches):
+ * residual planes, 1 (default) = between the first out-proj and the last FF2 the residual stream lives as two 16-bit planes (enum
+ *   tribe_c_planes: hi in the workspace's bf16 buffer, lo inside x itself) wherever the fused norms hold, M > 512 and every residual GEMM
+ *   runs the 256 x 256 role kernel; 0 = the f32 stream + bf16 copy.  x is f32 on entry and on return either way; the workspace is the same.
+ * residual tile hint: the tribe_gemm_desc.tile_hint of the out-proj / FF2 launches, 0 (default) or 2 (256 x 256 role kernel whatever
+ *   the shape: tests and A/B runs of small shapes). */
+int tribe_encoder_set_residual_planes(int32_t on);
+int tribe_encoder_set_residual_tile_hint(int32_t hint);
 size_t tribe_encoder_workspace_bytes(const tribe_encoder_desc* d);
 /* x: f32 [B*T, dim] residual stream, updated in place; y: final-normed output (bf16 or f32) [B*T, dim] */
 int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype,
