@@ -21,17 +21,19 @@ fp32 master parameters live in torch; bf16 packed copies are cached per paramete
 In `.eval()` / no-grad mode this fused path runs and records no autograd graph; in `.train()` mode with grad enabled
 `forward` composes the same arithmetic from the autograd functions of modeling_utils/autograd.py (HIP forward AND backward).
 
-Dropout (extensions `ff_dropout`, `layer_dropout`, `projector_dropout`; all 0 by default) acts on that autograd training path only: the
-fused path applies none, train mode under `no_grad` included (the reference's modules would drop there).  Each training pass with an active
-`ff_dropout` or `projector_dropout` draws one key (modeling_utils.models.common.draw_dropout_key: torch's default CPU generator) right
+Dropout (extensions `attn_dropout`, `ff_dropout`, `layer_dropout`, `projector_dropout`; all 0 by default) acts on that autograd training path
+only: the fused path applies none, train mode under `no_grad` included (the reference's modules would drop there).  Each training pass with
+an active `attn_dropout`, `ff_dropout` or `projector_dropout` draws one key (modeling_utils.models.common.draw_dropout_key: torch's default CPU generator) right
 after its modality-dropout draw -- the prediction pass and the contrastive pass each draw their own -- and every mask of the pass is
-tribe_dropout_apply with that key and a site:
+tribe_dropout_apply's definition with that key and a site:
     encoder feed-forward of layer i          (1 << 56) | i
+    attention probabilities of layer i       (4 << 56) | i                    (logical tensor [B * heads * T, T]; drawn inside the
+                                                                               softmax-dropout row kernels, see autograd.Attention)
     projector of modality m, hidden block j  (2 << 56) | (m << 16) | j        (m: position in feature_dims;
     contrastive head of m, hidden block j    (3 << 56) | (m << 16) | j         output dropout: j = MLP_OUT_BLOCK = 0xFFFF)
 `layer_dropout` follows x_transformers: per sub-layer (attention, then feed-forward, per depth) `random.random() < layer_dropout` skips
 norm, block and residual scaling; the draws use Python's `random` and are made only when layer_dropout > 0.  `last_dropout_key` and
-`last_layer_drops` keep the last pass's key and skip pattern.  With any of the three active the two passes never share latents.
+`last_layer_drops` keep the last pass's key and skip pattern.  With any of the four active the two passes never share latents.
 """
 
 from __future__ import annotations
@@ -51,7 +53,7 @@ from modeling_utils.models.transformer import TransformerEncoderConfig
 from tribe_hip import ops
 
 
-SITE_FF, SITE_PROJECTOR, SITE_HEAD = 1, 2, 3   # kinds of dropout site (module docstring); 0 = an Mlp used on its own
+SITE_FF, SITE_PROJECTOR, SITE_HEAD, SITE_ATTN = 1, 2, 3, 4   # kinds of dropout site (module docstring); 0 = an Mlp used on its own
 
 
 class FmriEncoderConfig(pydantic.BaseModel):
@@ -82,15 +84,18 @@ class FmriEncoderConfig(pydantic.BaseModel):
     # hidden sizes of every modality projector and contrastive head (MlpConfig.hidden_sizes): Linear -> LayerNorm -> GELU per size in
     # front of the output Linear.  None = the reference's single Linear (model.py:61, 64)
     projector_hidden_sizes: list[int] | None = None
-    # dropout of the training path (module docstring): on the encoder's feed-forward hidden (0 <= p < 1), x_transformers' stochastic
-    # depth per sub-layer (0 <= p <= 1), and MlpConfig.dropout of the MLP projectors / contrastive heads (0 <= p < 1; needs
-    # projector_hidden_sizes).  The reference hard-codes all three as 0 (model.py:62, 109-111)
+    # dropout of the training path (module docstring): on the encoder's attention probabilities and on its feed-forward hidden
+    # (0 <= p < 1 each), x_transformers' stochastic depth per sub-layer (0 <= p <= 1), and MlpConfig.dropout of the MLP projectors /
+    # contrastive heads (0 <= p < 1; needs projector_hidden_sizes).  The reference hard-codes all four as 0 (model.py:62, 109-111)
+    attn_dropout: float = 0.0
     ff_dropout: float = 0.0
     layer_dropout: float = 0.0
     projector_dropout: float = 0.0
 
     @pydantic.model_validator(mode="after")
     def _check_dropout(self) -> "FmriEncoderConfig":
+        if not 0.0 <= self.attn_dropout < 1.0:
+            raise ValueError(f"attn_dropout must satisfy 0 <= p < 1, got {self.attn_dropout}")
         if not 0.0 <= self.ff_dropout < 1.0:
             raise ValueError(f"ff_dropout must satisfy 0 <= p < 1, got {self.ff_dropout}")
         if not 0.0 <= self.layer_dropout <= 1.0:
@@ -137,7 +142,7 @@ class FmriEncoder(nn.Module):
         self.time_pos_embed = nn.Parameter(torch.randn(1, config.max_timesteps, hidden))
         if config.subject_embedding:
             self.subject_embed = nn.Embedding(config.n_subjects, hidden)
-        self.encoder = TransformerEncoderConfig(attn_dropout=0.0, ff_dropout=config.ff_dropout, layer_dropout=config.layer_dropout,
+        self.encoder = TransformerEncoderConfig(attn_dropout=config.attn_dropout, ff_dropout=config.ff_dropout, layer_dropout=config.layer_dropout,
                                                 depth=config.depth,
                                                 heads=config.heads, rotary_interleaved=config.rotary_interleaved,
                                                 legacy_scalenorm=config.legacy_scalenorm).build(dim=hidden)
@@ -178,7 +183,8 @@ class FmriEncoder(nn.Module):
 
     def _draw_pass_key(self) -> int | None:
         """The pass key of the HIP dropouts, drawn only when one is active (so at all-zero settings the RNG stream is untouched)."""
-        if self.encoder.ff_dropout > 0 or self.config.projector_dropout > 0:   # (the encoder module holds its own two rates)
+        enc = self.encoder   # (the encoder module holds its own rates)
+        if enc.ff_dropout > 0 or enc.attn_dropout > 0 or self.config.projector_dropout > 0:
             self.last_dropout_key = draw_dropout_key()
             return self.last_dropout_key
         return None
@@ -344,6 +350,7 @@ class FmriEncoder(nn.Module):
         drops = [random.random() < enc.layer_dropout for _ in range(2 * enc.depth)] if enc.layer_dropout > 0 else None
         self.last_layer_drops = drops
         fkey = self._pass_key if enc.ff_dropout > 0 else None
+        akey = self._pass_key if enc.attn_dropout > 0 else None
         for i in range(enc.depth):
             norms_a, attn, res_a = enc.layers[2 * i]
             norms_f, ff, res_f = enc.layers[2 * i + 1]
@@ -351,11 +358,12 @@ class FmriEncoder(nn.Module):
                 # the block input forks into norm(x) and the scaled residual; ScaleNormFork's backward sums the two gradients in its own kernel
                 xn, xr = ag.ScaleNormFork.apply(x, norms_a[0].g, gs, eps, res_a.residual_scale)
                 qkv = ag.QKVLinear.apply(xn, attn.to_q.weight, attn.to_k.weight, attn.to_v.weight)
+                adrop = () if akey is None else (enc.attn_dropout, akey, (SITE_ATTN << 56) | i)
                 if enc.rotary_emb_dim:
                     ao, _ = ag.RotaryAttention.apply(qkv, cos, sin, neg_sin, B, T, enc.heads, enc.dim_head, scale, enc.rotary_emb_dim,
-                                                     enc.rotary_interleaved)
+                                                     enc.rotary_interleaved, *adrop)
                 else:
-                    ao = ag.Attention.apply(qkv, B, T, enc.heads, enc.dim_head, scale)
+                    ao = ag.Attention.apply(qkv, B, T, enc.heads, enc.dim_head, scale, *adrop)
                 x = ag.Linear.apply(ao, attn.to_out.weight, None, xr, res_a.residual_scale, True, True)
             if not (drops and drops[2 * i + 1]):
                 xn, xr = ag.ScaleNormFork.apply(x, norms_f[0].g, gs, eps, res_f.residual_scale)

@@ -404,7 +404,15 @@ class Attention(torch.autograd.Function):
     log-sum-exp (dim_head 384) the backward keeps no f32 [B h, T, T] tensor and runs no softmax kernel: the score GEMM's epilogue writes
     P = exp2(scale log2e q.k - lse2[row]) (ACT_EXP2), the dO V^T GEMM's epilogue writes dS = scale (dP - D[row]) * P (ACT_MUL_AUX) with
     D = rowsum(dO * O) (FlashAttention-2's identity for rowsum(P * dP)); 12 bytes of HBM traffic per score instead of 28.  Other head
-    sizes (and FUSED_SOFTMAX = False) take the materialised S / dP + softmax kernels."""
+    sizes (and FUSED_SOFTMAX = False) take the materialised S / dP + softmax kernels.
+
+    Attention dropout (p > 0 with the pass key `seed` and the layer's `site`; x_transformers: attn = dropout(softmax(.)), out = attn v) never
+    enters the flash kernel, at any head size.  Forward, per chunk of sequences: f32 scores S = scale q k^T, ops.softmax_dropout_fwd (Pd =
+    softmax(S) * m as bf16, the row log-sum-exp of the undropped scores), O = Pd V; saved: qkv, out, lse -- no [B h, T, T] tensor outlives the
+    forward and no mask tensor exists.  Backward: D = rowsum(dO * O) (the identity holds since O = Pd V), P rebuilt by the ACT_EXP2 epilogue,
+    dPd = dO V^T in f32, ops.softmax_dropout_bwd (dS = scale P (m dPd - D); P overwritten by Pd = P m with the mask drawn again), then the three
+    gradient GEMMs with Pd for dV.  The mask is indexed by (b, h, i, j) through each chunk's first logical row: chunking does not move it.
+    p == 0 (the default) runs exactly the launches described above."""
 
     # f32 score bytes per chunk of sequences.  Same box, B = 16 (scripts/train_bench.py attn-chunk=N): 7 sequences (256 MiB) 112.0 ms,
     # 4 sequences 110.9, 2 sequences 117.4, 1 sequence 122.5 -- smaller chunks keep more of S / P / dP / dS in the Infinity Cache but
@@ -426,8 +434,38 @@ class Attention(torch.autograd.Function):
         return out
 
     @staticmethod
-    def forward(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float):
-        out = Attention._fwd(ctx, qkv, B, T, heads, dim_head, scale)
+    def _fwd_dropout(ctx, qkv, B: int, T: int, h: int, d: int, scale: float, p: float, seed: int, site: int):
+        inner, ld = h * d, 3 * h * d
+        dev = qkv.device
+        Tp = ops.round_up(T, 64)
+        chunk = max(1, min(B, Attention.CHUNK_BYTES // (h * T * Tp * 4)))
+        out = torch.empty(B * T, inner, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B, h, T, dtype=torch.float32, device=dev)
+        S = torch.empty(chunk * h * T, Tp, dtype=torch.float32, device=dev)
+        Pd = torch.empty(chunk * h * T, Tp, dtype=torch.bfloat16, device=dev)   # (the kernel zeroes the pad columns)
+        for b0 in range(0, B, chunk):
+            nb = min(chunk, B - b0)
+            rows, row0 = nb * h * T, b0 * T
+            _gemm(qkv, qkv, S, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale, batch1=nb, batch0=h, sA=(T * ld, d), sB=(T * ld, d),
+                  sC=(h * T * Tp, T * Tp), a_off=row0 * ld, b_off=row0 * ld + inner)
+            ops.softmax_dropout_fwd(S[:rows], p, seed, site, T=T, row0=b0 * h * T, out=Pd[:rows], lse=lse.view(-1)[b0 * h * T:b0 * h * T + rows])
+            # O[q, :] = sum_key Pd[q, key] V[key, :]: V per (b, h) as [d, Tp] with zero pad columns, like K for dQ in the backward
+            vT = _head_transpose(qkv, nb, h, T, d, ld, row0 * ld + 2 * inner)
+            _gemm(Pd, vT, out, lda=Tp, ldb=Tp, ldc=inner, M=T, N=d, K=Tp, batch1=nb, batch0=h, sA=(h * T * Tp, T * Tp), sB=(h * d * Tp, d * Tp),
+                  sC=(T * inner, d), c_off=row0 * inner)
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def _fwd_any(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float, seed: int, site: int):
+        ctx.drop = (float(p), int(seed), int(site))
+        if ctx.drop[0] > 0:
+            return Attention._fwd_dropout(ctx, qkv, B, T, heads, dim_head, scale, *ctx.drop)
+        return Attention._fwd(ctx, qkv, B, T, heads, dim_head, scale)
+
+    @staticmethod
+    def forward(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float = 0.0, seed: int = 0, site: int = 0):
+        out = Attention._fwd_any(ctx, qkv, B, T, heads, dim_head, scale, p, seed, site)
         ctx.meta = (B, T, heads, dim_head, scale)
         ctx.rotary = None
         return out
@@ -435,7 +473,8 @@ class Attention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         qkv = ctx.saved_tensors[0]
-        fused = len(ctx.saved_tensors) == 3
+        drop = ctx.drop[0] > 0
+        fused = len(ctx.saved_tensors) == 3 and not drop
         B, T, h, d, scale = ctx.meta
         inner, ld = h * d, 3 * h * d
         dev = qkv.device
@@ -450,6 +489,14 @@ class Attention(torch.autograd.Function):
             # (the GEMMs write columns < T only: the pad columns the K = T_pad products read stay zero)
             P = (torch.zeros if Tp != T else torch.empty)(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
             dS = (torch.zeros if Tp != T else torch.empty)(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
+        elif drop:
+            _, out, lse = ctx.saved_tensors
+            neg_lse = lse.neg()
+            neg_d = ops.rowdot_heads(dout, out, B, T, h, d, -scale)         # -scale * D: what softmax_dropout_bwd adds
+            # (ops.softmax_dropout_bwd zeroes the pad columns of P and dS)
+            P = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
+            dP = torch.empty(chunk * h, T, Tp, dtype=torch.float32, device=dev)
+            dS = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
         else:
             S = torch.empty(chunk * h, T, Tp, dtype=torch.float32, device=dev)
             P = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
@@ -469,6 +516,15 @@ class Attention(torch.autograd.Function):
                 _gemm(dout, qkv, dS, lda=inner, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale, act=_lib.ACT_MUL_AUX, aux=P, ld_aux=Tp, batch1=nb,
                       batch0=h, sA=(T * inner, d), sB=(T * ld, d), sC=(h * T * Tp, T * Tp), a_off=row0 * inner, b_off=v_off, row_bias=neg_d,
                       row_bias_off=b0 * h * T, sBias=(h * T, T))
+            elif drop:
+                # P = exp2(scale log2e Q K^T - lse2), dPd = dO V^T (f32), then dS = scale P (m dPd - D) and P <- Pd = P m in one row kernel
+                _gemm(qkv, qkv, P, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale * _LOG2E, act=_lib.ACT_EXP2, batch1=nb, batch0=h,
+                      sA=(T * ld, d), sB=(T * ld, d), sC=(h * T * Tp, T * Tp), a_off=q_off, b_off=k_off, row_bias=neg_lse, row_bias_off=b0 * h * T,
+                      sBias=(h * T, T))
+                _gemm(dout, qkv, dP, lda=inner, ldb=ld, ldc=Tp, M=T, N=T, K=d, batch1=nb, batch0=h, sA=(T * inner, d), sB=(T * ld, d),
+                      sC=(h * T * Tp, T * Tp), a_off=row0 * inner, b_off=v_off)
+                ops.softmax_dropout_bwd(P.view(-1, Tp)[:Z * T], dP.view(-1, Tp)[:Z * T], neg_d.view(-1)[b0 * h * T:b0 * h * T + Z * T], scale,
+                                        *ctx.drop, T=T, row0=b0 * h * T, dS=dS.view(-1, Tp)[:Z * T])
             else:
                 # S = scale * Q K^T ;  P = softmax(S)
                 _gemm(qkv, qkv, S, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale, batch1=nb, batch0=h, sA=(T * ld, d), sB=(T * ld, d),
@@ -503,26 +559,27 @@ class Attention(torch.autograd.Function):
         if ctx.rotary is not None:   # RotaryAttention: rotate dq, dk back in place -- dqkv is this function's own buffer
             cos, neg_sin, rot_dim, interleaved = ctx.rotary
             ops.rotary_(dqkv, T, h, d, rot_dim, cos, neg_sin, interleaved)
-        return dqkv, None, None, None, None, None
+        return (dqkv,) + (None,) * 8
 
 
 class RotaryAttention(torch.autograd.Function):
     """Rotary (in place on the q and k heads of the fused qkv buffer) + attention as ONE node: the backward rotates dq, dk by -theta in the
     gradient buffer it allocated itself.  As two nodes (Rotary, Attention) the rotation had to work on a clone of the incoming gradient
-    (302 MB copied per layer and step at B = 16) and negate the sine table every call."""
+    (302 MB copied per layer and step at B = 16) and negate the sine table every call.  (p, seed, site): Attention's attention dropout."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, neg_sin, B: int, T: int, heads: int, dim_head: int, scale: float, rot_dim: int, interleaved: bool):
+    def forward(ctx, qkv, cos, sin, neg_sin, B: int, T: int, heads: int, dim_head: int, scale: float, rot_dim: int, interleaved: bool,
+                p: float = 0.0, seed: int = 0, site: int = 0):
         ctx.mark_dirty(qkv)
         ops.rotary_(qkv, T, heads, dim_head, rot_dim, cos, sin, interleaved)
-        out = Attention._fwd(ctx, qkv, B, T, heads, dim_head, scale)
+        out = Attention._fwd_any(ctx, qkv, B, T, heads, dim_head, scale, p, seed, site)
         ctx.meta = (B, T, heads, dim_head, scale)
         ctx.rotary = (cos, neg_sin, rot_dim, interleaved)
         return out, qkv
 
     @staticmethod
     def backward(ctx, dout, _dqkv_alias):
-        return (Attention.backward(ctx, dout)[0],) + (None,) * 10
+        return (Attention.backward(ctx, dout)[0],) + (None,) * 13
 
 
 def _head_transpose(x: torch.Tensor, nb: int, h: int, T: int, d: int, ld: int, off: int) -> torch.Tensor:

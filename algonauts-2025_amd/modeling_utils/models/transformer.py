@@ -12,10 +12,12 @@ its "parity unpinned" status): pre-ScaleNorm, bias-free q/k/v/out projections, p
 the first max(dim_head // 2, 32) dims, fp32 softmax, scaled residual, GELU(erf) feed-forward,
 final ScaleNorm.
 
-Dropout fields: `ff_dropout` (0 <= p < 1, on the feed-forward hidden after the GELU) and `layer_dropout` (0 <= p <= 1, x_transformers'
-stochastic depth: per sub-layer `random.random() < layer_dropout` skips norm, block and residual) are stored on the module and act on
-the autograd training path of FmriEncoder only (algonauts2025/model.py); `HipEncoder.forward` / `forward_tokens`, the fused inference
-entry points, apply neither.  `attn_dropout` is accepted and inert: it would act inside the softmax of the attention kernels.
+Dropout fields: `attn_dropout` (0 <= p < 1, on the attention probabilities after the softmax: out = dropout(softmax(.)) v), `ff_dropout`
+(0 <= p < 1, on the feed-forward hidden after the GELU) and `layer_dropout` (0 <= p <= 1, x_transformers' stochastic depth: per sub-layer
+`random.random() < layer_dropout` skips norm, block and residual) are stored on the module and act on the autograd training path of
+FmriEncoder only (algonauts2025/model.py); `HipEncoder.forward` / `forward_tokens`, the fused inference entry points, apply none of them.
+An active `attn_dropout` takes the training path's attention off the flash kernel onto materialised scores and the softmax-dropout row
+kernels (modeling_utils.autograd.Attention); its masks are this build's counter-based ones, not torch's.
 """
 
 from __future__ import annotations
@@ -81,10 +83,11 @@ class _Rotary(nn.Module):
 class HipEncoder(nn.Module):
     def __init__(self, dim: int, depth: int, heads: int, dim_head: int, ff_mult: int = 4, rotary_pos_emb: bool = True,
                  scale_residual: bool = True, rotary_interleaved: bool = True, legacy_scalenorm: bool = False, ff_dropout: float = 0.0,
-                 layer_dropout: float = 0.0):
+                 layer_dropout: float = 0.0, attn_dropout: float = 0.0):
         super().__init__()
         self.dim, self.depth, self.heads, self.dim_head, self.ff_mult = dim, depth, heads, dim_head, ff_mult
         self.ff_dropout, self.layer_dropout = float(ff_dropout), float(layer_dropout)   # training path only (module docstring)
+        self.attn_dropout = float(attn_dropout)
         self.rotary_interleaved = rotary_interleaved
         self.rotary_emb_dim = max(dim_head // 2, 32) if rotary_pos_emb else 0
         if rotary_pos_emb:
@@ -209,9 +212,11 @@ class TransformerEncoderConfig(pydantic.BaseModel):
             raise ValueError(f"ff_dropout must satisfy 0 <= p < 1, got {self.ff_dropout}")
         if not 0.0 <= self.layer_dropout <= 1.0:
             raise ValueError(f"layer_dropout must satisfy 0 <= p <= 1, got {self.layer_dropout}")
-        # attn_dropout is accepted and inert (it lives inside the attention kernels' softmax); model.py passes 0.0.  attn_flash selects a
-        # kernel, not a result.  ff_dropout / layer_dropout act on FmriEncoder's autograd training path only (module docstring).
+        if not 0.0 <= self.attn_dropout < 1.0:
+            raise ValueError(f"attn_dropout must satisfy 0 <= p < 1, got {self.attn_dropout}")
+        # attn_flash selects a kernel, not a result.  attn_dropout / ff_dropout / layer_dropout act on FmriEncoder's autograd training path
+        # only (module docstring); the config's default attn_dropout is the reference's 0.1, FmriEncoderConfig's is 0.
         return HipEncoder(dim=dim, depth=self.depth, heads=self.heads, dim_head=dim // self.heads, ff_mult=self.ff_mult,
                           rotary_pos_emb=self.rotary_pos_emb, scale_residual=self.scale_residual,
                           rotary_interleaved=self.rotary_interleaved, legacy_scalenorm=self.legacy_scalenorm,
-                          ff_dropout=self.ff_dropout, layer_dropout=self.layer_dropout)
+                          ff_dropout=self.ff_dropout, layer_dropout=self.layer_dropout, attn_dropout=self.attn_dropout)

@@ -260,6 +260,9 @@ SIGNATURES = {
     "tribe_norm_act_path": (C.c_int, [vp, i64, i64, vp, vp, vp, i32, i64, vp, i32, i64]),
     "tribe_dropout_apply": (C.c_int, [vp, vp, i32, i64, i64, i64, i64, C.c_uint32, f32, C.c_uint64, C.c_uint64, vp]),
     "tribe_dropout_path": (C.c_int, [vp, vp, i32, i64, i64, i64]),
+    "tribe_softmax_dropout_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_uint32, f32, C.c_uint64, C.c_uint64, vp]),
+    "tribe_softmax_dropout_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, f32, i64, C.c_uint32, f32, C.c_uint64,
+                                            C.c_uint64, vp]),
     "tribe_quantize_fp8_fwd": (C.c_int, [vp, i32, i64, i64, i64, f32, vp, i64, vp]),
     "tribe_norm_quantize_fp8_fwd": (C.c_int, [vp, i64, i64, vp, vp, i32, f32, f32, vp, vp]),
     "tribe_absmax_fwd": (C.c_int, [vp, i32, i64, i64, i64, vp, i32, vp]),

@@ -485,6 +485,70 @@ def dropout_path(x: torch.Tensor, out: torch.Tensor | None = None) -> str:
     return DROPOUT_PATHS[lib().tribe_dropout_path(x.data_ptr(), y.data_ptr(), _DT[x.dtype], dim, ld_x, ld_y)]
 
 
+# attention dropout: the softmax row kernels with the mask drawn in registers (csrc/attn_dropout.hip)
+def _mask_args(what: str, p: float, seed: int, site: int, row0: int) -> tuple[int, float, int, int, int]:
+    threshold, keep = dropout_params(p)
+    for name, v in (("seed", seed), ("site", site)):
+        if not 0 <= int(v) < 1 << 64:
+            raise ValueError(f"{what}: {name} must fit 64 unsigned bits, got {v}")
+    if int(row0) < 0:
+        raise ValueError(f"{what}: row0 must be >= 0, got {row0}")
+    return int(row0), threshold, float(keep), int(seed), int(site)
+
+
+def softmax_dropout_fwd(S: torch.Tensor, p: float, seed: int, site: int, *, T: int | None = None, row0: int = 0,
+                        out: torch.Tensor | None = None, lse: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(Pd, lse2) of attention dropout's forward (tribe_softmax_dropout_fwd): S f32 [rows, >= T] with contiguous rows holds the scaled
+    scores in its leading T columns (default: all); Pd bf16 [rows, T_pad] = softmax(S) * m, m = dropout_apply's mask factor on the logical
+    [row0 + rows, T] tensor (element (r, j): idx = (row0 + r) * T + j), pad columns zero; lse2 f32 [rows] = the base-2 log-sum-exp of
+    attention_with_lse.  `out`: bf16 [rows, T_pad >= T], rows contiguous (default: a new tensor, T_pad = round_up(T, 64)); `lse`: f32
+    [rows].  p == 0 still runs the kernel (keep everything, scale 1): Pd then has tribe_softmax_fwd's bits."""
+    rows, width, ld_s = _row_view(S, torch.float32, "S")
+    T = width if T is None else int(T)
+    if not 0 < T <= width:
+        raise ValueError(f"softmax_dropout_fwd: T={T} outside (0, {width}]")
+    mask = _mask_args("softmax_dropout_fwd", p, seed, site, row0)
+    if out is None:
+        out = torch.empty(rows, round_up(T, 64), dtype=torch.bfloat16, device=S.device)
+    T_pad, ld_p = _row_view(out, torch.bfloat16, "out", rows, T)[1:]
+    if lse is None:
+        lse = torch.empty(rows, dtype=torch.float32, device=S.device)
+    _cuda(lse, torch.float32, "lse")
+    if lse.numel() != rows:
+        raise ValueError(f"softmax_dropout_fwd: lse has {lse.numel()} elements for {rows} rows")
+    check(lib().tribe_softmax_dropout_fwd(S.data_ptr(), out.data_ptr(), lse.data_ptr(), rows, T, T_pad, ld_s, ld_p, *mask, _stream()),
+          "tribe_softmax_dropout_fwd")
+    return out, lse
+
+
+def softmax_dropout_bwd(P: torch.Tensor, dPd: torch.Tensor, negD: torch.Tensor, scale: float, p: float, seed: int, site: int, *,
+                        T: int | None = None, row0: int = 0, dS: torch.Tensor | None = None,
+                        Pd: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(dS, Pd) of attention dropout's backward (tribe_softmax_dropout_bwd): P bf16 [rows, T_pad] the undropped softmax, dPd f32
+    [rows, >= T] = dO V^T in its leading T columns (default: all), negD f32 [rows] = -scale * rowsum(dO * O) (rowdot_heads with -scale);
+    the mask is drawn again from (p, seed, site, row0).  dS bf16 [rows, T_pad] = scale * P * (m * dPd - D), Pd = bf16(P * m), pad columns of
+    both zero.  `Pd` None: P is overwritten in place and handed back; `dS` None: a new tensor."""
+    rows, T_pad, ld_p = _row_view(P, torch.bfloat16, "P")
+    width, ld_dp = _row_view(dPd, torch.float32, "dPd", rows)[1:]
+    T = width if T is None else int(T)
+    if not 0 < T <= min(width, T_pad):
+        raise ValueError(f"softmax_dropout_bwd: T={T} outside (0, min({width}, {T_pad})]")
+    mask = _mask_args("softmax_dropout_bwd", p, seed, site, row0)
+    _cuda(negD, torch.float32, "negD")
+    if negD.numel() != rows:
+        raise ValueError(f"softmax_dropout_bwd: negD has {negD.numel()} elements for {rows} rows")
+    if dS is None:
+        dS = torch.empty(rows, T_pad, dtype=torch.bfloat16, device=P.device)
+    if Pd is None:
+        Pd = P
+    ld_ds, ld_pd = (_row_view(t, torch.bfloat16, name, rows, T_pad)[2] for t, name in ((dS, "dS"), (Pd, "Pd")))
+    if dS.shape[1] != T_pad or Pd.shape[1] != T_pad:
+        raise ValueError(f"softmax_dropout_bwd: dS {tuple(dS.shape)} and Pd {tuple(Pd.shape)} must have the shape of P {tuple(P.shape)}")
+    check(lib().tribe_softmax_dropout_bwd(P.data_ptr(), dPd.data_ptr(), negD.data_ptr(), dS.data_ptr(), Pd.data_ptr(), rows, T, T_pad, ld_p,
+                                          ld_dp, ld_ds, ld_pd, float(scale), *mask, _stream()), "tribe_softmax_dropout_bwd")
+    return dS, Pd
+
+
 def embedding(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     _cuda(table, (torch.float32, torch.bfloat16), "table")
     _cuda(ids, torch.int64, "ids")

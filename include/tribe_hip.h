@@ -887,6 +887,36 @@ int tribe_dropout_apply(const void* x, void* y, int32_t dtype /* TRIBE_F32 | TRI
  * 16-byte aligned), 1 = 8-byte accesses (four bf16 where 0 does not fit: multiples of four, 8-byte aligned), 2 = element accesses. */
 int tribe_dropout_path(const void* x, const void* y, int32_t dtype, int64_t dim, int64_t ld_x, int64_t ld_y);
 
+/* ---- attention dropout: the softmax row kernels of the training path with the mask drawn in registers (csrc/attn_dropout.hip) ----
+ * Both work on a slab of `rows` rows of the logical tensor [B * heads * T, T] that starts at its row `row0`.  Element (r, j) of the slab
+ * has idx = (row0 + r) * T + j (64-bit; from T, never from T_pad or a pitch) and is kept iff its word -- tribe_dropout_apply's: word
+ * idx & 3 of Philox4x32-10 with counter (lo32(idx >> 2), hi32(idx >> 2), lo32(site), hi32(site)), key (lo32(seed), hi32(seed)) -- is
+ * >= threshold.  m = scale_keep where kept, 0 where dropped; the host passes threshold = trunc(p * 2^32), scale_keep = (float)(1 / (1 - p)).
+ * The mask depends on (seed, site, row0 + r, j, T, threshold) alone -- not on how a caller cuts the rows into slabs -- and is never
+ * stored: the backward draws it again.  One Philox call serves four consecutive idx; a counter that straddles a row end (T % 4 != 0)
+ * is drawn by both rows.  One wave per row, no atomics: bit-reproducible.  Any T >= 1.
+ *
+ * tribe_softmax_dropout_fwd: S f32 [rows, T] (pitch ld_s), the scaled scores scale * q.k ->
+ *   Pd  bf16 [rows, T_pad] (pitch ld_p): kept: bf16(softmax(S) * scale_keep) -- the f32 softmax of tribe_softmax_fwd (row maximum
+ *       subtracted, same summation order: threshold = 0, scale_keep = 1 gives its bits), one f32 multiply, one rounding to bf16;
+ *       dropped: +0.0 by a select; columns T .. T_pad - 1: zero.
+ *   lse f32 [rows]: the base-2 log-sum-exp log2 sum_j 2^(S[r, j] * log2 e) of the UNDROPPED row, the convention of the fused attention
+ *       kernel's lse output: the ACT_EXP2 GEMM epilogue rebuilds P = exp2(scale * log2 e * q.k - lse) from it.
+ * tribe_softmax_dropout_bwd: P bf16 [rows, T_pad] (ld_p; the undropped softmax), dPd f32 [rows, T] (ld_dp; dO V^T, unscaled) and
+ *   negD f32 [rows] = -scale * D, D[r] = sum_j Pd[r, j] dPd[r, j] = sum_d dO[r, d] O[r, d] (what tribe_rowdot_heads_bf16 writes with
+ *   its scale argument set to -scale) ->
+ *   dS  bf16 [rows, T_pad] (ld_ds) = bf16(P * (scale * (m * dPd) + negD)) = scale * P * (m * dPd - D); columns >= T zero.  A dropped
+ *       score keeps the gradient -scale * P * D.
+ *   Pd  bf16 [rows, T_pad] (ld_pd) = bf16(P * m) (one f32 multiply), columns >= T zero.  Pd == P (with ld_pd == ld_p) overwrites P in
+ *       place; dS must be a buffer of its own.
+ * Errors (< 0, nothing launched): null pointer, rows / T <= 0, T_pad < T, row0 < 0, a pitch below its width (ld_s, ld_dp >= T; ld_p,
+ * ld_ds, ld_pd >= T_pad), dS aliasing P or Pd, Pd == P with another pitch, scale_keep not in [1, FLT_MAX]. */
+int tribe_softmax_dropout_fwd(const float* S, uint16_t* Pd, float* lse, int64_t rows, int64_t T, int64_t T_pad, int64_t ld_s, int64_t ld_p,
+                              int64_t row0, uint32_t threshold, float scale_keep, uint64_t seed, uint64_t site, void* stream);
+int tribe_softmax_dropout_bwd(const uint16_t* P, const float* dPd, const float* negD, uint16_t* dS, uint16_t* Pd, int64_t rows, int64_t T,
+                              int64_t T_pad, int64_t ld_p, int64_t ld_dp, int64_t ld_ds, int64_t ld_pd, float scale, int64_t row0,
+                              uint32_t threshold, float scale_keep, uint64_t seed, uint64_t site, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
