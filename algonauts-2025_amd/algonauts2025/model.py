@@ -34,6 +34,10 @@ tribe_dropout_apply's definition with that key and a site:
 `layer_dropout` follows x_transformers: per sub-layer (attention, then feed-forward, per depth) `random.random() < layer_dropout` skips
 norm, block and residual scaling; the draws use Python's `random` and are made only when layer_dropout > 0.  `last_dropout_key` and
 `last_layer_drops` keep the last pass's key and skip pattern.  With any of the four active the two passes never share latents.
+
+`causal` (extension, off by default) builds the encoder as x_transformers' Decoder: TR t attends to the stimulus up to t only.  The fused
+path gets it through the encoder's pack (tribe_encoder_fwd_ex), the training path hands it to autograd.RotaryAttention / Attention, which
+then take the materialised route with the causal row kernels at every attn_dropout; the dropouts above compose with it unchanged.
 """
 
 from __future__ import annotations
@@ -91,6 +95,8 @@ class FmriEncoderConfig(pydantic.BaseModel):
     ff_dropout: float = 0.0
     layer_dropout: float = 0.0
     projector_dropout: float = 0.0
+    # causal encoder (TransformerEncoderConfig.causal: TR t sees the stimulus up to t only); the reference leaves the field at its default
+    causal: bool = False
 
     @pydantic.model_validator(mode="after")
     def _check_dropout(self) -> "FmriEncoderConfig":
@@ -145,7 +151,7 @@ class FmriEncoder(nn.Module):
         self.encoder = TransformerEncoderConfig(attn_dropout=config.attn_dropout, ff_dropout=config.ff_dropout, layer_dropout=config.layer_dropout,
                                                 depth=config.depth,
                                                 heads=config.heads, rotary_interleaved=config.rotary_interleaved,
-                                                legacy_scalenorm=config.legacy_scalenorm).build(dim=hidden)
+                                                legacy_scalenorm=config.legacy_scalenorm, causal=config.causal).build(dim=hidden)
         self._packs = PackCache()
         self.last_dropout_key: int | None = None          # key of the last training pass with an active HIP dropout
         self.last_layer_drops: list[bool] | None = None   # its skipped sub-layers (attention, feed-forward per depth); None: layer_dropout 0
@@ -359,6 +365,8 @@ class FmriEncoder(nn.Module):
                 xn, xr = ag.ScaleNormFork.apply(x, norms_a[0].g, gs, eps, res_a.residual_scale)
                 qkv = ag.QKVLinear.apply(xn, attn.to_q.weight, attn.to_k.weight, attn.to_v.weight)
                 adrop = () if akey is None else (enc.attn_dropout, akey, (SITE_ATTN << 56) | i)
+                if enc.causal:   # the trailing argument of both functions: the mask takes the materialised route at every p
+                    adrop = (adrop or (0.0, 0, 0)) + (True,)
                 if enc.rotary_emb_dim:
                     ao, _ = ag.RotaryAttention.apply(qkv, cos, sin, neg_sin, B, T, enc.heads, enc.dim_head, scale, enc.rotary_emb_dim,
                                                      enc.rotary_interleaved, *adrop)

@@ -189,10 +189,12 @@ extern "C" size_t tribe_encoder_workspace_bytes(const tribe_encoder_desc* d) {
   return ws.off;
 }
 
-extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
+// the body of tribe_encoder_fwd (flags = 0) and tribe_encoder_fwd_ex
+static int encoder_fwd_body(const tribe_encoder_desc* d, uint32_t flags, float* x, void* y, int32_t y_dtype, void* workspace,
+                            size_t workspace_bytes, void* stream) {
   int rc = enc_validate(d);
   if (rc) return rc;
+  const bool causal = (flags & TRIBE_ENCODER_CAUSAL) != 0;
   TRIBE_REQUIRE(x && y && workspace, "tribe_encoder_fwd: null pointer");
   TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "tribe_encoder_fwd: workspace must be 256-byte aligned");
   Arena ws(workspace);
@@ -259,7 +261,7 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
     if (rc) return rc;
     // q heads and k heads are adjacent in the fused row.  The DH = 384 attention kernel rotates Q while it loads its Q fragments
     // (interleaved pairs; bit-identical arithmetic), so only the k heads go through the stand-alone pass: half its 805 MB.
-    const bool q_in_attn = g_attn_mode == 0 && d->rot_dim > 0 && d->rotary_interleaved == 1 && d->rot_dim % 16 == 0 &&
+    const bool q_in_attn = !causal && g_attn_mode == 0 && d->rot_dim > 0 && d->rotary_interleaved == 1 && d->rot_dim % 16 == 0 &&
                            tribe_internal_attention_rotates_q(d->dim_head);
     if (d->rot_dim > 0) {
       rc = q_in_attn ? tribe_rotary_fwd(qkv + inner, M, d->T, 3 * inner, d->heads, d->dim_head, d->rot_dim, d->cos_tab, d->sin_tab,
@@ -268,9 +270,20 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
                                         d->rotary_interleaved, stream);
       if (rc) return rc;
     }
-    rc = q_in_attn ? tribe_internal_attention_fused_qrot(qkv, d->B, d->T, d->heads, d->dim_head, scale, ao, d->cos_tab, d->sin_tab,
-                                                         d->rot_dim, (hipStream_t)stream)
-                   : tribe_attention_fwd(qkv, d->B, d->T, d->heads, d->dim_head, scale, ao, p.attn_ws, p.attn_bytes, stream);
+    if (causal) {   // the fused kernel under the mask (the 16-row kernel at every head size): q and k arrive rotated
+      tribe_attention_desc a{};
+      a.q = qkv; a.k = qkv + inner; a.v = qkv + 2 * inner;
+      a.ld_q = a.ld_k = a.ld_v = 3 * inner;
+      a.out = ao; a.ld_out = inner;
+      a.B = d->B; a.T = d->T;
+      a.heads_q = a.heads_kv = d->heads; a.dim_head = d->dim_head; a.causal = 1;
+      a.scale = scale;
+      rc = tribe_attention_fwd_ex(&a, stream);
+    } else {
+      rc = q_in_attn ? tribe_internal_attention_fused_qrot(qkv, d->B, d->T, d->heads, d->dim_head, scale, ao, d->cos_tab, d->sin_tab,
+                                                           d->rot_dim, (hipStream_t)stream)
+                     : tribe_attention_fwd(qkv, d->B, d->T, d->heads, d->dim_head, scale, ao, p.attn_ws, p.attn_bytes, stream);
+    }
     if (rc) return rc;
     g = residual_gemm(l, false, planes);
     if (fuse) {
@@ -302,6 +315,18 @@ extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y,
     if (rc) return rc;
   }
   return tribe_scalenorm_fwd(x, M, dim, d->final_norm_g, d->norm_gain_scale, d->norm_eps, y, y_dtype, stream);
+}
+
+extern "C" int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  return encoder_fwd_body(d, 0u, x, y, y_dtype, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tribe_encoder_fwd_ex(const tribe_encoder_desc* d, uint32_t flags, float* x, void* y, int32_t y_dtype, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE((flags & ~TRIBE_ENCODER_CAUSAL) == 0, "tribe_encoder_fwd_ex: unknown flag bits 0x%x (known: TRIBE_ENCODER_CAUSAL = 1)",
+                (unsigned)(flags & ~TRIBE_ENCODER_CAUSAL));
+  return encoder_fwd_body(d, flags, x, y, y_dtype, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tribe_voxel_head_fwd(const uint16_t* x, int64_t B, int64_t T, int64_t C_pad, const uint16_t* w_packed, int64_t S,

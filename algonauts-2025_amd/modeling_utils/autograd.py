@@ -412,7 +412,12 @@ class Attention(torch.autograd.Function):
     forward and no mask tensor exists.  Backward: D = rowsum(dO * O) (the identity holds since O = Pd V), P rebuilt by the ACT_EXP2 epilogue,
     dPd = dO V^T in f32, ops.softmax_dropout_bwd (dS = scale P (m dPd - D); P overwritten by Pd = P m with the mask drawn again), then the three
     gradient GEMMs with Pd for dV.  The mask is indexed by (b, h, i, j) through each chunk's first logical row: chunking does not move it.
-    p == 0 (the default) runs exactly the launches described above."""
+    p == 0 (the default) runs exactly the launches described above.
+
+    causal=True (x_transformers' Decoder: keys j > query i masked before the softmax) takes that materialised route at EVERY p, p == 0 included
+    (threshold 0, scale_keep 1), with ops.softmax_causal_fwd / ops.softmax_causal_bwd in place of the two row kernels: they compute the lower
+    triangle only, write exact zeros above it and never read what the mask-unaware ACT_EXP2 epilogue left there.  The GEMMs still compute
+    full squares (skipping their upper-triangle tiles is the GEMM's business).  causal=False launches what it always did."""
 
     # f32 score bytes per chunk of sequences.  Same box, B = 16 (scripts/train_bench.py attn-chunk=N): 7 sequences (256 MiB) 112.0 ms,
     # 4 sequences 110.9, 2 sequences 117.4, 1 sequence 122.5 -- smaller chunks keep more of S / P / dP / dS in the Infinity Cache but
@@ -434,7 +439,8 @@ class Attention(torch.autograd.Function):
         return out
 
     @staticmethod
-    def _fwd_dropout(ctx, qkv, B: int, T: int, h: int, d: int, scale: float, p: float, seed: int, site: int):
+    def _fwd_dropout(ctx, qkv, B: int, T: int, h: int, d: int, scale: float, p: float, seed: int, site: int, causal: bool = False):
+        softmax_fwd = ops.softmax_causal_fwd if causal else ops.softmax_dropout_fwd
         inner, ld = h * d, 3 * h * d
         dev = qkv.device
         Tp = ops.round_up(T, 64)
@@ -448,7 +454,7 @@ class Attention(torch.autograd.Function):
             rows, row0 = nb * h * T, b0 * T
             _gemm(qkv, qkv, S, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale, batch1=nb, batch0=h, sA=(T * ld, d), sB=(T * ld, d),
                   sC=(h * T * Tp, T * Tp), a_off=row0 * ld, b_off=row0 * ld + inner)
-            ops.softmax_dropout_fwd(S[:rows], p, seed, site, T=T, row0=b0 * h * T, out=Pd[:rows], lse=lse.view(-1)[b0 * h * T:b0 * h * T + rows])
+            softmax_fwd(S[:rows], p, seed, site, T=T, row0=b0 * h * T, out=Pd[:rows], lse=lse.view(-1)[b0 * h * T:b0 * h * T + rows])
             # O[q, :] = sum_key Pd[q, key] V[key, :]: V per (b, h) as [d, Tp] with zero pad columns, like K for dQ in the backward
             vT = _head_transpose(qkv, nb, h, T, d, ld, row0 * ld + 2 * inner)
             _gemm(Pd, vT, out, lda=Tp, ldb=Tp, ldc=inner, M=T, N=d, K=Tp, batch1=nb, batch0=h, sA=(h * T * Tp, T * Tp), sB=(h * d * Tp, d * Tp),
@@ -457,15 +463,17 @@ class Attention(torch.autograd.Function):
         return out
 
     @staticmethod
-    def _fwd_any(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float, seed: int, site: int):
+    def _fwd_any(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float, seed: int, site: int, causal: bool = False):
         ctx.drop = (float(p), int(seed), int(site))
-        if ctx.drop[0] > 0:
-            return Attention._fwd_dropout(ctx, qkv, B, T, heads, dim_head, scale, *ctx.drop)
+        ctx.causal = bool(causal)
+        if ctx.drop[0] > 0 or ctx.causal:
+            return Attention._fwd_dropout(ctx, qkv, B, T, heads, dim_head, scale, *ctx.drop, causal=ctx.causal)
         return Attention._fwd(ctx, qkv, B, T, heads, dim_head, scale)
 
     @staticmethod
-    def forward(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float = 0.0, seed: int = 0, site: int = 0):
-        out = Attention._fwd_any(ctx, qkv, B, T, heads, dim_head, scale, p, seed, site)
+    def forward(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float = 0.0, seed: int = 0, site: int = 0,
+                causal: bool = False):
+        out = Attention._fwd_any(ctx, qkv, B, T, heads, dim_head, scale, p, seed, site, causal)
         ctx.meta = (B, T, heads, dim_head, scale)
         ctx.rotary = None
         return out
@@ -473,7 +481,8 @@ class Attention(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         qkv = ctx.saved_tensors[0]
-        drop = ctx.drop[0] > 0
+        drop = ctx.drop[0] > 0 or ctx.causal   # the materialised route with a masked row kernel
+        softmax_bwd = ops.softmax_causal_bwd if ctx.causal else ops.softmax_dropout_bwd
         fused = len(ctx.saved_tensors) == 3 and not drop
         B, T, h, d, scale = ctx.meta
         inner, ld = h * d, 3 * h * d
@@ -493,7 +502,7 @@ class Attention(torch.autograd.Function):
             _, out, lse = ctx.saved_tensors
             neg_lse = lse.neg()
             neg_d = ops.rowdot_heads(dout, out, B, T, h, d, -scale)         # -scale * D: what softmax_dropout_bwd adds
-            # (ops.softmax_dropout_bwd zeroes the pad columns of P and dS)
+            # (the row kernel zeroes the pad columns of P and dS; the causal one also everything above the diagonal)
             P = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
             dP = torch.empty(chunk * h, T, Tp, dtype=torch.float32, device=dev)
             dS = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
@@ -523,8 +532,8 @@ class Attention(torch.autograd.Function):
                       sBias=(h * T, T))
                 _gemm(dout, qkv, dP, lda=inner, ldb=ld, ldc=Tp, M=T, N=T, K=d, batch1=nb, batch0=h, sA=(T * inner, d), sB=(T * ld, d),
                       sC=(h * T * Tp, T * Tp), a_off=row0 * inner, b_off=v_off)
-                ops.softmax_dropout_bwd(P.view(-1, Tp)[:Z * T], dP.view(-1, Tp)[:Z * T], neg_d.view(-1)[b0 * h * T:b0 * h * T + Z * T], scale,
-                                        *ctx.drop, T=T, row0=b0 * h * T, dS=dS.view(-1, Tp)[:Z * T])
+                softmax_bwd(P.view(-1, Tp)[:Z * T], dP.view(-1, Tp)[:Z * T], neg_d.view(-1)[b0 * h * T:b0 * h * T + Z * T], scale, *ctx.drop,
+                            T=T, row0=b0 * h * T, dS=dS.view(-1, Tp)[:Z * T])
             else:
                 # S = scale * Q K^T ;  P = softmax(S)
                 _gemm(qkv, qkv, S, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale, batch1=nb, batch0=h, sA=(T * ld, d), sB=(T * ld, d),
@@ -559,27 +568,28 @@ class Attention(torch.autograd.Function):
         if ctx.rotary is not None:   # RotaryAttention: rotate dq, dk back in place -- dqkv is this function's own buffer
             cos, neg_sin, rot_dim, interleaved = ctx.rotary
             ops.rotary_(dqkv, T, h, d, rot_dim, cos, neg_sin, interleaved)
-        return (dqkv,) + (None,) * 8
+        return (dqkv,) + (None,) * 9
 
 
 class RotaryAttention(torch.autograd.Function):
     """Rotary (in place on the q and k heads of the fused qkv buffer) + attention as ONE node: the backward rotates dq, dk by -theta in the
     gradient buffer it allocated itself.  As two nodes (Rotary, Attention) the rotation had to work on a clone of the incoming gradient
-    (302 MB copied per layer and step at B = 16) and negate the sine table every call.  (p, seed, site): Attention's attention dropout."""
+    (302 MB copied per layer and step at B = 16) and negate the sine table every call.  (p, seed, site): Attention's attention dropout;
+    causal: Attention's mask."""
 
     @staticmethod
     def forward(ctx, qkv, cos, sin, neg_sin, B: int, T: int, heads: int, dim_head: int, scale: float, rot_dim: int, interleaved: bool,
-                p: float = 0.0, seed: int = 0, site: int = 0):
+                p: float = 0.0, seed: int = 0, site: int = 0, causal: bool = False):
         ctx.mark_dirty(qkv)
         ops.rotary_(qkv, T, heads, dim_head, rot_dim, cos, sin, interleaved)
-        out = Attention._fwd_any(ctx, qkv, B, T, heads, dim_head, scale, p, seed, site)
+        out = Attention._fwd_any(ctx, qkv, B, T, heads, dim_head, scale, p, seed, site, causal)
         ctx.meta = (B, T, heads, dim_head, scale)
         ctx.rotary = (cos, neg_sin, rot_dim, interleaved)
         return out, qkv
 
     @staticmethod
     def backward(ctx, dout, _dqkv_alias):
-        return (Attention.backward(ctx, dout)[0],) + (None,) * 13
+        return (Attention.backward(ctx, dout)[0],) + (None,) * 14
 
 
 def _head_transpose(x: torch.Tensor, nb: int, h: int, T: int, d: int, ld: int, off: int) -> torch.Tensor:

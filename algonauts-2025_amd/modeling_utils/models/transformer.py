@@ -18,6 +18,13 @@ Dropout fields: `attn_dropout` (0 <= p < 1, on the attention probabilities after
 FmriEncoder only (algonauts2025/model.py); `HipEncoder.forward` / `forward_tokens`, the fused inference entry points, apply none of them.
 An active `attn_dropout` takes the training path's attention off the flash kernel onto materialised scores and the softmax-dropout row
 kernels (modeling_utils.autograd.Attention); its masks are this build's counter-based ones, not torch's.
+
+`causal=True` is x_transformers' `Decoder`: the `Encoder` plus a mask -- scores with key index > query index are filled with -finfo.max before
+the softmax -- with the same parameters, `state_dict` keys and rotary.  `HipEncoder(causal=True)` hands the flag to its EncoderPack: the
+fused inference path runs tribe_encoder_fwd_ex with TRIBE_ENCODER_CAUSAL (q and k heads through the stand-alone rotary, then the causal
+flash kernel).  The training path (FmriEncoder) passes it to modeling_utils.autograd.Attention / RotaryAttention, which then take the
+materialised route at every attn_dropout, 0 included, with the causal softmax row kernels (csrc/attn_causal.hip); the three dropout fields
+compose with it unchanged.  dim_head must be one the flash kernel is built for (64, 128, 192, 384).
 """
 
 from __future__ import annotations
@@ -83,8 +90,9 @@ class _Rotary(nn.Module):
 class HipEncoder(nn.Module):
     def __init__(self, dim: int, depth: int, heads: int, dim_head: int, ff_mult: int = 4, rotary_pos_emb: bool = True,
                  scale_residual: bool = True, rotary_interleaved: bool = True, legacy_scalenorm: bool = False, ff_dropout: float = 0.0,
-                 layer_dropout: float = 0.0, attn_dropout: float = 0.0):
+                 layer_dropout: float = 0.0, attn_dropout: float = 0.0, causal: bool = False):
         super().__init__()
+        self.causal = bool(causal)   # x_transformers' Decoder mask (module docstring); no parameter depends on it
         self.dim, self.depth, self.heads, self.dim_head, self.ff_mult = dim, depth, heads, dim_head, ff_mult
         self.ff_dropout, self.layer_dropout = float(ff_dropout), float(layer_dropout)   # training path only (module docstring)
         self.attn_dropout = float(attn_dropout)
@@ -126,7 +134,8 @@ class HipEncoder(nn.Module):
     def packed(self) -> ops.EncoderPack:
         def build() -> ops.EncoderPack:
             pack = ops.EncoderPack(self.dim, self.depth, self.heads, self.dim_head, int(self.dim * self.ff_mult),
-                                   self.rotary_emb_dim, self.rotary_interleaved, self.final_norm.gain_scale, self.final_norm.eps)
+                                   self.rotary_emb_dim, self.rotary_interleaved, self.final_norm.gain_scale, self.final_norm.eps,
+                                   causal=self.causal)
             keep = pack.keep
 
             def own(t: torch.Tensor) -> int:
@@ -154,7 +163,8 @@ class HipEncoder(nn.Module):
                 pack.inv_freq = self.rotary_pos_emb.inv_freq
             return pack
 
-        return self._packs.get("enc", self._sources(), build)
+        # one cache slot per mask: a pack built before `causal` was flipped is not served afterwards
+        return self._packs.get("enc_causal" if self.causal else "enc", self._sources(), build)
 
     # -- forward ----------------------------------------------------------------------------
     def forward_tokens(self, x2d: torch.Tensor, B: int, T: int, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
@@ -201,7 +211,7 @@ class TransformerEncoderConfig(pydantic.BaseModel):
         if dim < 256:
             raise ValueError(f"dim ({dim}) is less than 256, which causes weird bug in x-transformers")
         unsupported = {
-            "cross_attend": self.cross_attend, "causal": self.causal, "use_rmsnorm": self.use_rmsnorm,
+            "cross_attend": self.cross_attend, "use_rmsnorm": self.use_rmsnorm,
             "rel_pos_bias": self.rel_pos_bias, "alibi_pos_bias": self.alibi_pos_bias, "rotary_xpos": self.rotary_xpos,
             "residual_attn": self.residual_attn, "not use_scalenorm": not self.use_scalenorm,
         }
@@ -219,4 +229,5 @@ class TransformerEncoderConfig(pydantic.BaseModel):
         return HipEncoder(dim=dim, depth=self.depth, heads=self.heads, dim_head=dim // self.heads, ff_mult=self.ff_mult,
                           rotary_pos_emb=self.rotary_pos_emb, scale_residual=self.scale_residual,
                           rotary_interleaved=self.rotary_interleaved, legacy_scalenorm=self.legacy_scalenorm,
-                          ff_dropout=self.ff_dropout, layer_dropout=self.layer_dropout, attn_dropout=self.attn_dropout)
+                          ff_dropout=self.ff_dropout, layer_dropout=self.layer_dropout, attn_dropout=self.attn_dropout,
+                          causal=self.causal)

@@ -20,6 +20,7 @@ F32, BF16, F64 = 0, 1, 2
 F32_PLANES_OUT, F32_PLANES_INOUT, F32_PLANES_IN = 16, 17, 18   # enum tribe_c_planes (tribe_gemm_desc.c_dtype of the residual role kernels)
 ACT_NONE, ACT_GELU, ACT_SWIGLU, ACT_SILU, ACT_GLU, ACT_GELU_BWD, ACT_EXP2, ACT_MUL_AUX = 0, 1, 2, 3, 4, 5, 6, 7
 ACT_RELU, ACT_ELU = 8, 9   # tribe_norm_act_fwd / tribe_norm_act_bwd only
+ENCODER_CAUSAL = 1         # tribe_encoder_fwd_ex flags (TRIBE_ENCODER_CAUSAL)
 BIAS_NONE, BIAS_COL, BIAS_ROW = 0, 1, 2
 ROLES = ["generic", "projector", "qkv", "attn_scores", "attn_pv", "out_proj", "ff1", "ff2", "voxel_head", "attention"]
 ROLE = {name: index for index, name in enumerate(ROLES)}   # tribe_gemm_desc.role (and the prof_end slots) by name
@@ -263,6 +264,9 @@ SIGNATURES = {
     "tribe_softmax_dropout_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_uint32, f32, C.c_uint64, C.c_uint64, vp]),
     "tribe_softmax_dropout_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, f32, i64, C.c_uint32, f32, C.c_uint64,
                                             C.c_uint64, vp]),
+    "tribe_softmax_causal_fwd": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_uint32, f32, C.c_uint64, C.c_uint64, vp]),
+    "tribe_softmax_causal_bwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, f32, i64, C.c_uint32, f32, C.c_uint64,
+                                           C.c_uint64, vp]),
     "tribe_quantize_fp8_fwd": (C.c_int, [vp, i32, i64, i64, i64, f32, vp, i64, vp]),
     "tribe_norm_quantize_fp8_fwd": (C.c_int, [vp, i64, i64, vp, vp, i32, f32, f32, vp, vp]),
     "tribe_absmax_fwd": (C.c_int, [vp, i32, i64, i64, i64, vp, i32, vp]),
@@ -281,6 +285,7 @@ SIGNATURES = {
     "tribe_encoder_set_residual_tile_hint": (C.c_int, [i32]),
     "tribe_encoder_workspace_bytes": (sz, [C.POINTER(EncoderDesc)]),
     "tribe_encoder_fwd": (C.c_int, [C.POINTER(EncoderDesc), vp, vp, i32, vp, sz, vp]),
+    "tribe_encoder_fwd_ex": (C.c_int, [C.POINTER(EncoderDesc), C.c_uint32, vp, vp, i32, vp, sz, vp]),
     "tribe_voxel_head_fwd": (C.c_int, [vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp]),
     "tribe_adaptive_avg_pool_fwd": (C.c_int, [vp, i64, i64, vp, i64, vp]),
     "tribe_mse_fwd": (C.c_int, [vp, vp, i64, vp, vp, sz, vp]),

@@ -496,18 +496,14 @@ def _mask_args(what: str, p: float, seed: int, site: int, row0: int) -> tuple[in
     return int(row0), threshold, float(keep), int(seed), int(site)
 
 
-def softmax_dropout_fwd(S: torch.Tensor, p: float, seed: int, site: int, *, T: int | None = None, row0: int = 0,
-                        out: torch.Tensor | None = None, lse: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
-    """(Pd, lse2) of attention dropout's forward (tribe_softmax_dropout_fwd): S f32 [rows, >= T] with contiguous rows holds the scaled
-    scores in its leading T columns (default: all); Pd bf16 [rows, T_pad] = softmax(S) * m, m = dropout_apply's mask factor on the logical
-    [row0 + rows, T] tensor (element (r, j): idx = (row0 + r) * T + j), pad columns zero; lse2 f32 [rows] = the base-2 log-sum-exp of
-    attention_with_lse.  `out`: bf16 [rows, T_pad >= T], rows contiguous (default: a new tensor, T_pad = round_up(T, 64)); `lse`: f32
-    [rows].  p == 0 still runs the kernel (keep everything, scale 1): Pd then has tribe_softmax_fwd's bits."""
+def _softmax_rows_fwd(what: str, S: torch.Tensor, p: float, seed: int, site: int, T: int | None, row0: int, out: torch.Tensor | None,
+                      lse: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The body of softmax_dropout_fwd and softmax_causal_fwd: one validation, the entry point tribe_<what>."""
     rows, width, ld_s = _row_view(S, torch.float32, "S")
     T = width if T is None else int(T)
     if not 0 < T <= width:
-        raise ValueError(f"softmax_dropout_fwd: T={T} outside (0, {width}]")
-    mask = _mask_args("softmax_dropout_fwd", p, seed, site, row0)
+        raise ValueError(f"{what}: T={T} outside (0, {width}]")
+    mask = _mask_args(what, p, seed, site, row0)
     if out is None:
         out = torch.empty(rows, round_up(T, 64), dtype=torch.bfloat16, device=S.device)
     T_pad, ld_p = _row_view(out, torch.bfloat16, "out", rows, T)[1:]
@@ -515,10 +511,44 @@ def softmax_dropout_fwd(S: torch.Tensor, p: float, seed: int, site: int, *, T: i
         lse = torch.empty(rows, dtype=torch.float32, device=S.device)
     _cuda(lse, torch.float32, "lse")
     if lse.numel() != rows:
-        raise ValueError(f"softmax_dropout_fwd: lse has {lse.numel()} elements for {rows} rows")
-    check(lib().tribe_softmax_dropout_fwd(S.data_ptr(), out.data_ptr(), lse.data_ptr(), rows, T, T_pad, ld_s, ld_p, *mask, _stream()),
-          "tribe_softmax_dropout_fwd")
+        raise ValueError(f"{what}: lse has {lse.numel()} elements for {rows} rows")
+    check(getattr(lib(), "tribe_" + what)(S.data_ptr(), out.data_ptr(), lse.data_ptr(), rows, T, T_pad, ld_s, ld_p, *mask, _stream()),
+          "tribe_" + what)
     return out, lse
+
+
+def _softmax_rows_bwd(what: str, P: torch.Tensor, dPd: torch.Tensor, negD: torch.Tensor, scale: float, p: float, seed: int, site: int,
+                      T: int | None, row0: int, dS: torch.Tensor | None, Pd: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The body of softmax_dropout_bwd and softmax_causal_bwd."""
+    rows, T_pad, ld_p = _row_view(P, torch.bfloat16, "P")
+    width, ld_dp = _row_view(dPd, torch.float32, "dPd", rows)[1:]
+    T = width if T is None else int(T)
+    if not 0 < T <= min(width, T_pad):
+        raise ValueError(f"{what}: T={T} outside (0, min({width}, {T_pad})]")
+    mask = _mask_args(what, p, seed, site, row0)
+    _cuda(negD, torch.float32, "negD")
+    if negD.numel() != rows:
+        raise ValueError(f"{what}: negD has {negD.numel()} elements for {rows} rows")
+    if dS is None:
+        dS = torch.empty(rows, T_pad, dtype=torch.bfloat16, device=P.device)
+    if Pd is None:
+        Pd = P
+    ld_ds, ld_pd = (_row_view(t, torch.bfloat16, name, rows, T_pad)[2] for t, name in ((dS, "dS"), (Pd, "Pd")))
+    if dS.shape[1] != T_pad or Pd.shape[1] != T_pad:
+        raise ValueError(f"{what}: dS {tuple(dS.shape)} and Pd {tuple(Pd.shape)} must have the shape of P {tuple(P.shape)}")
+    check(getattr(lib(), "tribe_" + what)(P.data_ptr(), dPd.data_ptr(), negD.data_ptr(), dS.data_ptr(), Pd.data_ptr(), rows, T, T_pad, ld_p,
+                                           ld_dp, ld_ds, ld_pd, float(scale), *mask, _stream()), "tribe_" + what)
+    return dS, Pd
+
+
+def softmax_dropout_fwd(S: torch.Tensor, p: float, seed: int, site: int, *, T: int | None = None, row0: int = 0,
+                        out: torch.Tensor | None = None, lse: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(Pd, lse2) of attention dropout's forward (tribe_softmax_dropout_fwd): S f32 [rows, >= T] with contiguous rows holds the scaled
+    scores in its leading T columns (default: all); Pd bf16 [rows, T_pad] = softmax(S) * m, m = dropout_apply's mask factor on the logical
+    [row0 + rows, T] tensor (element (r, j): idx = (row0 + r) * T + j), pad columns zero; lse2 f32 [rows] = the base-2 log-sum-exp of
+    attention_with_lse.  `out`: bf16 [rows, T_pad >= T], rows contiguous (default: a new tensor, T_pad = round_up(T, 64)); `lse`: f32
+    [rows].  p == 0 still runs the kernel (keep everything, scale 1): Pd then has tribe_softmax_fwd's bits."""
+    return _softmax_rows_fwd("softmax_dropout_fwd", S, p, seed, site, T, row0, out, lse)
 
 
 def softmax_dropout_bwd(P: torch.Tensor, dPd: torch.Tensor, negD: torch.Tensor, scale: float, p: float, seed: int, site: int, *,
@@ -528,25 +558,25 @@ def softmax_dropout_bwd(P: torch.Tensor, dPd: torch.Tensor, negD: torch.Tensor, 
     [rows, >= T] = dO V^T in its leading T columns (default: all), negD f32 [rows] = -scale * rowsum(dO * O) (rowdot_heads with -scale);
     the mask is drawn again from (p, seed, site, row0).  dS bf16 [rows, T_pad] = scale * P * (m * dPd - D), Pd = bf16(P * m), pad columns of
     both zero.  `Pd` None: P is overwritten in place and handed back; `dS` None: a new tensor."""
-    rows, T_pad, ld_p = _row_view(P, torch.bfloat16, "P")
-    width, ld_dp = _row_view(dPd, torch.float32, "dPd", rows)[1:]
-    T = width if T is None else int(T)
-    if not 0 < T <= min(width, T_pad):
-        raise ValueError(f"softmax_dropout_bwd: T={T} outside (0, min({width}, {T_pad})]")
-    mask = _mask_args("softmax_dropout_bwd", p, seed, site, row0)
-    _cuda(negD, torch.float32, "negD")
-    if negD.numel() != rows:
-        raise ValueError(f"softmax_dropout_bwd: negD has {negD.numel()} elements for {rows} rows")
-    if dS is None:
-        dS = torch.empty(rows, T_pad, dtype=torch.bfloat16, device=P.device)
-    if Pd is None:
-        Pd = P
-    ld_ds, ld_pd = (_row_view(t, torch.bfloat16, name, rows, T_pad)[2] for t, name in ((dS, "dS"), (Pd, "Pd")))
-    if dS.shape[1] != T_pad or Pd.shape[1] != T_pad:
-        raise ValueError(f"softmax_dropout_bwd: dS {tuple(dS.shape)} and Pd {tuple(Pd.shape)} must have the shape of P {tuple(P.shape)}")
-    check(lib().tribe_softmax_dropout_bwd(P.data_ptr(), dPd.data_ptr(), negD.data_ptr(), dS.data_ptr(), Pd.data_ptr(), rows, T, T_pad, ld_p,
-                                          ld_dp, ld_ds, ld_pd, float(scale), *mask, _stream()), "tribe_softmax_dropout_bwd")
-    return dS, Pd
+    return _softmax_rows_bwd("softmax_dropout_bwd", P, dPd, negD, scale, p, seed, site, T, row0, dS, Pd)
+
+
+def softmax_causal_fwd(S: torch.Tensor, p: float, seed: int, site: int, *, T: int | None = None, row0: int = 0,
+                       out: torch.Tensor | None = None, lse: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """softmax_dropout_fwd under a causal mask (tribe_softmax_causal_fwd): row r of S is query i = (row0 + r) % T of the logical
+    [B * heads * T, T] tensor.  Pd[r, j <= i] = softmax(S[r, :i + 1])[j] * m with softmax_dropout_fwd's mask m, +0.0 in every other column of
+    `out` (pad columns included); lse2 = the base-2 log-sum-exp of the visible scores.  S above the diagonal is not used.  p == 0 is causal
+    attention without dropout.  Same arguments, validation and defaults as softmax_dropout_fwd."""
+    return _softmax_rows_fwd("softmax_causal_fwd", S, p, seed, site, T, row0, out, lse)
+
+
+def softmax_causal_bwd(P: torch.Tensor, dPd: torch.Tensor, negD: torch.Tensor, scale: float, p: float, seed: int, site: int, *,
+                       T: int | None = None, row0: int = 0, dS: torch.Tensor | None = None,
+                       Pd: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """softmax_dropout_bwd under a causal mask (tribe_softmax_causal_bwd): for j <= i = (row0 + r) % T, dS = scale * P * (m * dPd - D) and
+    Pd = bf16(P * m); +0.0 in every other column of both.  P and dPd above the diagonal are neither used nor kept: P may come from an
+    ACT_EXP2 epilogue that knows no mask (and holds inf there).  Same arguments, validation and defaults as softmax_dropout_bwd."""
+    return _softmax_rows_bwd("softmax_causal_bwd", P, dPd, negD, scale, p, seed, site, T, row0, dS, Pd)
 
 
 def embedding(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
@@ -680,7 +710,8 @@ class EncoderPack:
     tribe_encoder_fwd.  Built from (and kept alive next to) the fp32 master parameters."""
 
     def __init__(self, dim: int, depth: int, heads: int, dim_head: int, ff_inner: int, rot_dim: int, rotary_interleaved: bool,
-                 norm_gain_scale: float, norm_eps: float):
+                 norm_gain_scale: float, norm_eps: float, causal: bool = False):
+        self.causal = bool(causal)   # tribe_encoder_fwd_ex with TRIBE_ENCODER_CAUSAL
         self.dim, self.depth, self.heads, self.dim_head, self.ff_inner = dim, depth, heads, dim_head, ff_inner
         self.rot_dim, self.rotary_interleaved = rot_dim, rotary_interleaved
         self.norm_gain_scale, self.norm_eps = norm_gain_scale, norm_eps
@@ -718,6 +749,10 @@ def encoder_fwd(x: torch.Tensor, pack: EncoderPack, B: int, T: int, out_dtype: t
     y = torch.empty(B * T, pack.dim, dtype=out_dtype, device=x.device)
     nbytes = lib().tribe_encoder_workspace_bytes(C.byref(d))
     ws = workspace(nbytes, x.device)
+    if pack.causal:
+        check(lib().tribe_encoder_fwd_ex(C.byref(d), _lib.ENCODER_CAUSAL, x.data_ptr(), y.data_ptr(), _DT[out_dtype], ws.data_ptr(), ws.numel(),
+                                         _stream()), "tribe_encoder_fwd_ex")
+        return y
     check(lib().tribe_encoder_fwd(C.byref(d), x.data_ptr(), y.data_ptr(), _DT[out_dtype], ws.data_ptr(), ws.numel(), _stream()),
           "tribe_encoder_fwd")
     return y

@@ -300,6 +300,12 @@ size_t tribe_encoder_workspace_bytes(const tribe_encoder_desc* d);
 /* x: f32 [B*T, dim] residual stream, updated in place; y: final-normed output (bf16 or f32) [B*T, dim] */
 int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* tribe_encoder_fwd with option bits; flags = 0 is tribe_encoder_fwd itself, an unknown bit is an error.  The workspace is the same.
+ * TRIBE_ENCODER_CAUSAL: every layer attends under a causal mask (key <= query; x_transformers' Decoder).  q and k heads are rotated by
+ *   tribe_rotary_fwd and the attention is tribe_attention_fwd_ex with causal = 1: dim_head in {64, 128, 192, 384}. */
+#define TRIBE_ENCODER_CAUSAL 1u
+int tribe_encoder_fwd_ex(const tribe_encoder_desc* d, uint32_t flags, float* x, void* y, int32_t y_dtype,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * a16-a18: building blocks of the frozen extractors (HF transformers architectures)
@@ -916,6 +922,23 @@ int tribe_softmax_dropout_fwd(const float* S, uint16_t* Pd, float* lse, int64_t 
 int tribe_softmax_dropout_bwd(const uint16_t* P, const float* dPd, const float* negD, uint16_t* dS, uint16_t* Pd, int64_t rows, int64_t T,
                               int64_t T_pad, int64_t ld_p, int64_t ld_dp, int64_t ld_ds, int64_t ld_pd, float scale, int64_t row0,
                               uint32_t threshold, float scale_keep, uint64_t seed, uint64_t site, void* stream);
+
+/* ---- causal attention of the training path: the same two row kernels under a causal mask (csrc/attn_causal.hip) ----
+ * Arguments, mask, errors and kernel selection are those of tribe_softmax_dropout_fwd / _bwd, plus one rule: row r of the slab is query
+ * i = (row0 + r) % T of the logical tensor [B * heads * T, T], and columns j > i are masked (x_transformers' Decoder: scores with key >
+ * query filled with -finfo.max before the softmax).  threshold = 0, scale_keep = 1 is causal attention without dropout.
+ *   fwd: for j <= i Pd[r, j] = bf16(softmax(S[r, 0..i])[j] * m); +0.0 bits for every other column below T_pad; lse[r] = the base-2
+ *        log-sum-exp of the visible scores.
+ *   bwd: for j <= i dS = bf16(P * (scale * (m * dPd) + negD)) and Pd = bf16(P * m); +0.0 bits for every other column below T_pad of both.
+ *        Pd == P (with ld_pd == ld_p) is allowed.
+ * A row loads, draws and computes its quads 0 .. i / 4 only and zero-fills the rest; S, P and dPd above the diagonal are never used, so P
+ * may come straight from a TRIBE_ACT_EXP2 epilogue that knows no mask (there it may hold inf).  On the columns <= i the results, lse
+ * included, have the bits of the non-causal kernels run on the same scores with -inf written above the diagonal. */
+int tribe_softmax_causal_fwd(const float* S, uint16_t* Pd, float* lse, int64_t rows, int64_t T, int64_t T_pad, int64_t ld_s, int64_t ld_p,
+                             int64_t row0, uint32_t threshold, float scale_keep, uint64_t seed, uint64_t site, void* stream);
+int tribe_softmax_causal_bwd(const uint16_t* P, const float* dPd, const float* negD, uint16_t* dS, uint16_t* Pd, int64_t rows, int64_t T,
+                             int64_t T_pad, int64_t ld_p, int64_t ld_dp, int64_t ld_ds, int64_t ld_pd, float scale, int64_t row0,
+                             uint32_t threshold, float scale_keep, uint64_t seed, uint64_t site, void* stream);
 
 #ifdef __cplusplus
 }
