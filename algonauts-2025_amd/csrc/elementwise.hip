@@ -3,6 +3,7 @@
 // kernels (roofline: HBM bandwidth); loads/stores are 8-16 B per lane where the
 // layout allows.
 #include "common.h"
+#include "softmax_row.h"
 
 namespace {
 
@@ -698,19 +699,16 @@ __global__ __launch_bounds__(256) void softmax_kernel(const float* __restrict__ 
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= R) return;
   const float* s = S + row * ld_s;
-  float m = -INFINITY;
-  for (int64_t i = lane; i < T; i += 64) m = fmaxf(m, s[i]);
-  m = wave_max(m);
-  float sum = 0.f;
-  for (int64_t i = lane; i < T; i += 64) sum += __expf(s[i] - m);
-  sum = wave_sum(sum);
+  const auto [m, sum] = softmax_row_walk(s, T, lane);
   const float inv = 1.0f / sum;
   unsigned short* p = P + row * ld_p;
   for (int64_t i = lane; i < T_pad; i += 64) p[i] = (i < T) ? f32_to_bf16(__expf(s[i] - m) * inv) : (unsigned short)0;
 }
 
 // the same softmax with the row in registers (T = 256 NV, no padding): S is read once with 16-byte loads, exp is evaluated once per
-// score (the walk above evaluates it twice and moves 4 / 2 bytes per lane and instruction), P leaves as 8-byte stores
+// score (the walk above evaluates it twice and moves 4 / 2 bytes per lane and instruction), P leaves as 8-byte stores.  Its statistics are
+// softmax_row_reg's (softmax_row.h) written out: through the helper hipcc commutes some of the adds and schedules the exps differently
+// (same bits, other machine code), and this kernel is on the inference path
 template <int NV>
 __global__ __launch_bounds__(256) void softmax_reg_kernel(const float* __restrict__ S, int64_t R, int64_t ld_s, unsigned short* __restrict__ P,
                                                           int64_t ld_p) {

@@ -1,5 +1,5 @@
 // Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85): the counter-based generator behind the
-// bootstrap draws (bootstrap.hip) and the dropout masks (dropout.hip, attn_dropout.hip).  Pinned by the known-answer vectors of tests/test_bootstrap_host.py.
+// bootstrap draws (bootstrap.hip) and the dropout masks (dropout.hip, attn_softmax.hip).  Pinned by the known-answer vectors of tests/test_bootstrap_host.py.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -23,7 +23,7 @@ kernels (modeling_utils.autograd.Attention); its masks are this build's counter-
 the softmax -- with the same parameters, `state_dict` keys and rotary.  `HipEncoder(causal=True)` hands the flag to its EncoderPack: the
 fused inference path runs tribe_encoder_fwd_ex with TRIBE_ENCODER_CAUSAL (q and k heads through the stand-alone rotary, then the causal
 flash kernel).  The training path (FmriEncoder) passes it to modeling_utils.autograd.Attention / RotaryAttention, which then take the
-materialised route at every attn_dropout, 0 included, with the causal softmax row kernels (csrc/attn_causal.hip); the three dropout fields
+materialised route at every attn_dropout, 0 included, with the causal softmax row kernels (csrc/attn_softmax.hip); the three dropout fields
 compose with it unchanged.  dim_head must be one the flash kernel is built for (64, 128, 192, 384).
 """
 

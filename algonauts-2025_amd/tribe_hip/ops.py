@@ -485,7 +485,7 @@ def dropout_path(x: torch.Tensor, out: torch.Tensor | None = None) -> str:
     return DROPOUT_PATHS[lib().tribe_dropout_path(x.data_ptr(), y.data_ptr(), _DT[x.dtype], dim, ld_x, ld_y)]
 
 
-# attention dropout: the softmax row kernels with the mask drawn in registers (csrc/attn_dropout.hip)
+# attention dropout: the softmax row kernels with the mask drawn in registers (csrc/attn_softmax.hip)
 def _mask_args(what: str, p: float, seed: int, site: int, row0: int) -> tuple[int, float, int, int, int]:
     threshold, keep = dropout_params(p)
     for name, v in (("seed", seed), ("site", site)):

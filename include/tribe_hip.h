@@ -893,8 +893,9 @@ int tribe_dropout_apply(const void* x, void* y, int32_t dtype /* TRIBE_F32 | TRI
  * 16-byte aligned), 1 = 8-byte accesses (four bf16 where 0 does not fit: multiples of four, 8-byte aligned), 2 = element accesses. */
 int tribe_dropout_path(const void* x, const void* y, int32_t dtype, int64_t dim, int64_t ld_x, int64_t ld_y);
 
-/* ---- attention dropout: the softmax row kernels of the training path with the mask drawn in registers (csrc/attn_dropout.hip) ----
- * Both work on a slab of `rows` rows of the logical tensor [B * heads * T, T] that starts at its row `row0`.  Element (r, j) of the slab
+/* ---- the softmax row kernels of the training path (non-causal and causal), dropout mask drawn in registers (csrc/attn_softmax.hip) ----
+ * One contract for the four entry points; the causal pair adds the one rule stated after it.
+ * All work on a slab of `rows` rows of the logical tensor [B * heads * T, T] that starts at its row `row0`.  Element (r, j) of the slab
  * has idx = (row0 + r) * T + j (64-bit; from T, never from T_pad or a pitch) and is kept iff its word -- tribe_dropout_apply's: word
  * idx & 3 of Philox4x32-10 with counter (lo32(idx >> 2), hi32(idx >> 2), lo32(site), hi32(site)), key (lo32(seed), hi32(seed)) -- is
  * >= threshold.  m = scale_keep where kept, 0 where dropped; the host passes threshold = trunc(p * 2^32), scale_keep = (float)(1 / (1 - p)).
@@ -923,8 +924,8 @@ int tribe_softmax_dropout_bwd(const uint16_t* P, const float* dPd, const float* 
                               int64_t T_pad, int64_t ld_p, int64_t ld_dp, int64_t ld_ds, int64_t ld_pd, float scale, int64_t row0,
                               uint32_t threshold, float scale_keep, uint64_t seed, uint64_t site, void* stream);
 
-/* ---- causal attention of the training path: the same two row kernels under a causal mask (csrc/attn_causal.hip) ----
- * Arguments, mask, errors and kernel selection are those of tribe_softmax_dropout_fwd / _bwd, plus one rule: row r of the slab is query
+/* The causal rule (the same kernel templates, compiled with CAUSAL): arguments, mask, errors and kernel selection are those of
+ * tribe_softmax_dropout_fwd / _bwd, and row r of the slab is query
  * i = (row0 + r) % T of the logical tensor [B * heads * T, T], and columns j > i are masked (x_transformers' Decoder: scores with key >
  * query filled with -finfo.max before the softmax).  threshold = 0, scale_keep = 1 is causal attention without dropout.
  *   fwd: for j <= i Pd[r, j] = bf16(softmax(S[r, 0..i])[j] * m); +0.0 bits for every other column below T_pad; lse[r] = the base-2

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED0123456789AB
 SITE = (4 << 56) | 1
-KERNEL_SHAPES = [(33, 33), (280, 70), (64, 64), (576, 192), (1192, 298), (8, 1024), (3, 1500)]   # rows x T
+KERNEL_SHAPES = [(33, 33), (280, 70), (64, 64), (576, 192), (1192, 298), (8, 256), (8, 512), (8, 1024), (8, 2048), (3, 1500)]   # rows x T
 SPLITS = {33: 13, 280: 101, 64: 6, 576: 101, 1192: 597, 8: 3, 3: 1}                               # rows -> a first-slab size, never % 4 == 0
 SCALE = 0.125
 

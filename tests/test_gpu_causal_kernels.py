@@ -1,4 +1,4 @@
-"""GPU: the causal softmax row kernels (ops.softmax_causal_fwd / _bwd, csrc/attn_causal.hip).
+"""GPU: the causal softmax row kernels (ops.softmax_causal_fwd / _bwd, csrc/attn_softmax.hip).
 
 Main handle: on the columns j <= i the results -- lse included -- must have the BITS of ops.softmax_dropout_fwd / _bwd run on the same scores
 with -inf (forward) or zeros (backward) above the diagonal, since the causal kernels keep their kernel selection, lane ownership and summation
@@ -24,7 +24,8 @@ pytestmark = pytest.mark.gpu
 
 SEED = 0x5EED0123456789AB
 SITE = (4 << 56) | 1
-SLABS = [(33, 33, 0), (140, 70, 35), (64, 64, 0), (200, 192, 100), (300, 298, 290), (8, 256, 252), (8, 1024, 1020), (5, 1500, 1497)]
+SLABS = [(33, 33, 0), (140, 70, 35), (64, 64, 0), (200, 192, 100), (300, 298, 290), (8, 256, 252), (8, 512, 508), (8, 1024, 1020),
+         (8, 2048, 2044), (5, 1500, 1497)]
 SPLITS = {33: 13, 140: 51, 64: 6, 200: 101, 300: 151, 8: 3, 5: 1}                    # rows -> a first-slab size, never % 4 == 0
 PS = [0.0, 0.1, 0.5]
 SCALE = 0.125
