@@ -378,24 +378,66 @@ class ScaleNormFork(torch.autograd.Function):
         return dx, dg, None, None, None
 
 
-class Rotary(torch.autograd.Function):
-    """In-place partial rotary on the q and k heads of a fused qkv buffer (returns the same storage)."""
+_HeadSlice = tp.Tuple[torch.Tensor, int, int]
 
-    @staticmethod
-    def forward(ctx, qkv, cos, sin, T: int, heads: int, dim_head: int, rot_dim: int, interleaved: bool):
-        ctx.mark_dirty(qkv)
-        ops.rotary_(qkv, T, heads, dim_head, rot_dim, cos, sin, interleaved)
-        ctx.save_for_backward(cos, sin)
-        ctx.meta = (T, heads, dim_head, rot_dim, interleaved)
-        return qkv
 
-    @staticmethod
-    def backward(ctx, dqkv):
-        cos, sin = ctx.saved_tensors
-        T, heads, dim_head, rot_dim, interleaved = ctx.meta
-        d = dqkv.contiguous().clone() if not dqkv.is_contiguous() else dqkv.clone()
-        ops.rotary_(d, T, heads, dim_head, rot_dim, cos, (-sin).contiguous(), interleaved)  # rotation by -theta = transpose
-        return d, None, None, None, None, None, None, None
+class _HeadGemms:
+    """The batched per-(sequence, head) products of Attention for the sequences [b0, b0 + nb) of one chunk, each form stated once.
+    A head slice of a row-major [B*T, ld] buffer is (tensor, ld, element offset of the chunk's first row, head 0): q / k / v build it for
+    the column blocks of a fused [B*T, 3 * h * d] buffer (qkv, dqkv), o for a [B*T, h * d] one (out, dout).  A score buffer (S, P, dP, dS)
+    is [sequences * h * T, Tp], Tp = T padded to 64."""
+
+    def __init__(self, h: int, T: int, d: int, nb: int = 0, b0: int = 0) -> None:
+        self.h, self.T, self.d, self.nb, self.Tp = h, T, d, nb, ops.round_up(T, 64)
+        inner = h * d
+        self.q, self.k, self.v = (lambda x, off=b0 * T * 3 * inner + i * inner: (x, 3 * inner, off) for i in range(3))
+        self.o = lambda x: (x, inner, b0 * T * inner)
+        self.rows = slice(b0 * h * T, (b0 + nb) * h * T)   # the chunk's rows (b, h, t) of the logical [B * h * T, T] scores, of lse and D
+        self.n = nb * h * T                                # how many: the leading rows of a score buffer that the chunk uses
+        self.s_scores = (h * T * self.Tp, T * self.Tp)     # batch strides (sequence, head) of a score buffer
+        self.reads_transposed = T % 64 == 0 and d % 8 == 0   # dV, dK: `weighted_t` in place of `weighted`
+
+    def chunk_size(self, B: int, score_bytes: int) -> int:
+        """Sequences per chunk: one f32 score buffer stays within score_bytes."""
+        return max(1, min(B, score_bytes // (self.h * self.T * self.Tp * 4)))
+
+    def chunks(self, B: int, size: int) -> tp.Iterator[_HeadGemms]:
+        return (_HeadGemms(self.h, self.T, self.d, min(size, B - b0), b0) for b0 in range(0, B, size))
+
+    def score_buffer(self, size: int, dtype: torch.dtype, device: torch.device, zero_pad: bool = False) -> torch.Tensor:
+        """For chunks of `size` sequences; zero_pad: the pad columns are zero from the start, for writers that leave them alone."""
+        return (torch.zeros if zero_pad and self.Tp != self.T else torch.empty)(size * self.h * self.T, self.Tp, dtype=dtype, device=device)
+
+    def _s_heads(self, ld: int) -> tuple[int, int]:
+        return self.T * ld, self.d                         # batch strides (sequence, head) of a head slice
+
+    def transposed(self, x: _HeadSlice) -> torch.Tensor:
+        """A head slice as bf16 [nb * h, d, Tp] with zero pad columns: the second factor of `weighted`."""
+        return _head_transpose(x[0], self.nb, self.h, self.T, self.d, x[1], x[2])
+
+    def scores(self, a: _HeadSlice, b: _HeadSlice, out: torch.Tensor, alpha: float = 1.0, act: int = _lib.ACT_NONE,
+               aux: torch.Tensor | None = None, row_bias: torch.Tensor | None = None) -> None:
+        """out[(b, h), i, j] = act(alpha * sum_c a[b, i, h, c] * b[b, j, h, c] + row_bias[b, h, i]): two head slices -> a score buffer
+        (q k^T, dO v^T).  aux: the score buffer `act` reads; row_bias: f32 over ALL logical rows [B * h * T], the chunk's are picked here."""
+        (ta, lda, a_off), (tb, ldb, b_off) = a, b
+        _gemm(ta, tb, out, lda=lda, ldb=ldb, ldc=self.Tp, M=self.T, N=self.T, K=self.d, alpha=alpha, act=act, aux=aux, ld_aux=self.Tp,
+              batch1=self.nb, batch0=self.h, sA=self._s_heads(lda), sB=self._s_heads(ldb), sC=self.s_scores, a_off=a_off, b_off=b_off,
+              row_bias=row_bias, row_bias_off=self.rows.start, sBias=(self.h * self.T, self.T))
+
+    def weighted(self, w: torch.Tensor, xT: torch.Tensor, out: _HeadSlice) -> None:
+        """out[b, i, h, :] = sum_j w[(b, h), i, j] x[b, j, h, :]: a score buffer times xT = transposed(x) -> a head slice.  The reduction
+        runs along the ROWS of x, hence its per-(b, h) transposed copy [d, Tp]; K = Tp: the pad columns of both factors are zero."""
+        to, ldc, c_off = out
+        _gemm(w, xT, to, lda=self.Tp, ldb=self.Tp, ldc=ldc, M=self.T, N=self.d, K=self.Tp, batch1=self.nb, batch0=self.h, sA=self.s_scores,
+              sB=(self.h * self.d * self.Tp, self.d * self.Tp), sC=self._s_heads(ldc), c_off=c_off)
+
+    def weighted_t(self, w: torch.Tensor, x: _HeadSlice, out: _HeadSlice) -> None:
+        """out[b, j, h, :] = sum_i w[(b, h), i, j] x[b, i, h, :] (where reads_transposed): both factors have the reduction index i on their
+        ROWS -- the transposed-operand form of the GEMM (desc.trans_ab) reads the score buffer [T, Tp] and the head slice as they lie: no
+        P^T, dS^T ([B h, T, T] each), q^T, dO^T."""
+        (tx, ldx, x_off), (to, ldc, c_off) = x, out
+        _gemm(w, tx, to, lda=self.Tp, ldb=ldx, ldc=ldc, M=self.T, N=self.d, K=self.T, batch1=self.nb, batch0=self.h, sA=self.s_scores,
+              sB=self._s_heads(ldx), sC=self._s_heads(ldc), b_off=x_off, c_off=c_off, trans_ab=True)
 
 
 class Attention(torch.autograd.Function):
@@ -429,142 +471,96 @@ class Attention(torch.autograd.Function):
     FUSED_SOFTMAX = True
 
     @staticmethod
-    def _fwd(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float):
-        if Attention.FUSED_SOFTMAX and ops.attention_lse_supported(dim_head):
+    def _fwd_masked(qkv, B: int, T: int, h: int, d: int, scale: float, drop: tuple[float, int, int], causal: bool):
+        """(out, lse) of the materialised forward under a mask: attention dropout, the causal mask (at any p, 0 included) or both."""
+        softmax_fwd = ops.softmax_causal_fwd if causal else ops.softmax_dropout_fwd
+        dev = qkv.device
+        heads = _HeadGemms(h, T, d)
+        size = heads.chunk_size(B, Attention.CHUNK_BYTES)
+        out = torch.empty(B * T, h * d, dtype=torch.bfloat16, device=dev)
+        lse = torch.empty(B, h, T, dtype=torch.float32, device=dev)
+        S = heads.score_buffer(size, torch.float32, dev)
+        Pd = heads.score_buffer(size, torch.bfloat16, dev)   # (the kernel zeroes the pad columns)
+        for g in heads.chunks(B, size):
+            g.scores(g.q(qkv), g.k(qkv), S, alpha=scale)
+            softmax_fwd(S[:g.n], *drop, T=T, row0=g.rows.start, out=Pd[:g.n], lse=lse.view(-1)[g.rows])
+            g.weighted(Pd, g.transposed(g.v(qkv)), g.o(out))   # O[q, :] = sum_key Pd[q, key] V[key, :]
+        return out, lse
+
+    @staticmethod
+    def _fwd_any(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float, seed: int, site: int, causal: bool = False):
+        """Runs the forward of the route and records it in ctx.route: "masked" (dropout and / or causal), "fused" (the flash kernel hands
+        over its log-sum-exp) or "materialised"."""
+        ctx.meta = (B, T, heads, dim_head, scale)
+        ctx.drop = (float(p), int(seed), int(site))
+        ctx.causal = bool(causal)
+        if ctx.drop[0] > 0 or ctx.causal:
+            ctx.route = "masked"
+            out, lse = Attention._fwd_masked(qkv, B, T, heads, dim_head, scale, ctx.drop, ctx.causal)
+            ctx.save_for_backward(qkv, out, lse)
+        elif Attention.FUSED_SOFTMAX and ops.attention_lse_supported(dim_head):
+            ctx.route = "fused"
             out, lse = ops.attention_with_lse(qkv, B, T, heads, dim_head, scale)
             ctx.save_for_backward(qkv, out, lse)
         else:
+            ctx.route = "materialised"
             out = ops.attention(qkv, B, T, heads, dim_head, scale)
             ctx.save_for_backward(qkv)
         return out
 
     @staticmethod
-    def _fwd_dropout(ctx, qkv, B: int, T: int, h: int, d: int, scale: float, p: float, seed: int, site: int, causal: bool = False):
-        softmax_fwd = ops.softmax_causal_fwd if causal else ops.softmax_dropout_fwd
-        inner, ld = h * d, 3 * h * d
-        dev = qkv.device
-        Tp = ops.round_up(T, 64)
-        chunk = max(1, min(B, Attention.CHUNK_BYTES // (h * T * Tp * 4)))
-        out = torch.empty(B * T, inner, dtype=torch.bfloat16, device=dev)
-        lse = torch.empty(B, h, T, dtype=torch.float32, device=dev)
-        S = torch.empty(chunk * h * T, Tp, dtype=torch.float32, device=dev)
-        Pd = torch.empty(chunk * h * T, Tp, dtype=torch.bfloat16, device=dev)   # (the kernel zeroes the pad columns)
-        for b0 in range(0, B, chunk):
-            nb = min(chunk, B - b0)
-            rows, row0 = nb * h * T, b0 * T
-            _gemm(qkv, qkv, S, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale, batch1=nb, batch0=h, sA=(T * ld, d), sB=(T * ld, d),
-                  sC=(h * T * Tp, T * Tp), a_off=row0 * ld, b_off=row0 * ld + inner)
-            softmax_fwd(S[:rows], p, seed, site, T=T, row0=b0 * h * T, out=Pd[:rows], lse=lse.view(-1)[b0 * h * T:b0 * h * T + rows])
-            # O[q, :] = sum_key Pd[q, key] V[key, :]: V per (b, h) as [d, Tp] with zero pad columns, like K for dQ in the backward
-            vT = _head_transpose(qkv, nb, h, T, d, ld, row0 * ld + 2 * inner)
-            _gemm(Pd, vT, out, lda=Tp, ldb=Tp, ldc=inner, M=T, N=d, K=Tp, batch1=nb, batch0=h, sA=(h * T * Tp, T * Tp), sB=(h * d * Tp, d * Tp),
-                  sC=(T * inner, d), c_off=row0 * inner)
-        ctx.save_for_backward(qkv, out, lse)
-        return out
-
-    @staticmethod
-    def _fwd_any(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float, seed: int, site: int, causal: bool = False):
-        ctx.drop = (float(p), int(seed), int(site))
-        ctx.causal = bool(causal)
-        if ctx.drop[0] > 0 or ctx.causal:
-            return Attention._fwd_dropout(ctx, qkv, B, T, heads, dim_head, scale, *ctx.drop, causal=ctx.causal)
-        return Attention._fwd(ctx, qkv, B, T, heads, dim_head, scale)
-
-    @staticmethod
     def forward(ctx, qkv, B: int, T: int, heads: int, dim_head: int, scale: float, p: float = 0.0, seed: int = 0, site: int = 0,
                 causal: bool = False):
         out = Attention._fwd_any(ctx, qkv, B, T, heads, dim_head, scale, p, seed, site, causal)
-        ctx.meta = (B, T, heads, dim_head, scale)
         ctx.rotary = None
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv = ctx.saved_tensors[0]
-        drop = ctx.drop[0] > 0 or ctx.causal   # the materialised route with a masked row kernel
+        qkv, route = ctx.saved_tensors[0], ctx.route
         softmax_bwd = ops.softmax_causal_bwd if ctx.causal else ops.softmax_dropout_bwd
-        fused = len(ctx.saved_tensors) == 3 and not drop
         B, T, h, d, scale = ctx.meta
-        inner, ld = h * d, 3 * h * d
         dev = qkv.device
         dout = cast_bf16(dout)
         dqkv = torch.empty_like(qkv)
-        Tp = ops.round_up(T, 64)
-        chunk = max(1, min(B, (Attention.CHUNK_BYTES_FUSED if fused else Attention.CHUNK_BYTES) // (h * T * Tp * 4)))
-        if fused:
+        heads = _HeadGemms(h, T, d)
+        Tp = heads.Tp
+        size = heads.chunk_size(B, Attention.CHUNK_BYTES_FUSED if route == "fused" else Attention.CHUNK_BYTES)
+        if route != "materialised":
             _, out, lse = ctx.saved_tensors
-            neg_lse = lse.neg()                                             # the row biases of the two epilogues, [B, h, T] f32
-            neg_d = ops.rowdot_heads(dout, out, B, T, h, d, -scale)
-            # (the GEMMs write columns < T only: the pad columns the K = T_pad products read stay zero)
-            P = (torch.zeros if Tp != T else torch.empty)(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
-            dS = (torch.zeros if Tp != T else torch.empty)(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
-        elif drop:
-            _, out, lse = ctx.saved_tensors
-            neg_lse = lse.neg()
-            neg_d = ops.rowdot_heads(dout, out, B, T, h, d, -scale)         # -scale * D: what softmax_dropout_bwd adds
-            # (the row kernel zeroes the pad columns of P and dS; the causal one also everything above the diagonal)
-            P = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
-            dP = torch.empty(chunk * h, T, Tp, dtype=torch.float32, device=dev)
-            dS = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
-        else:
-            S = torch.empty(chunk * h, T, Tp, dtype=torch.float32, device=dev)
-            P = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
-            dP = torch.empty(chunk * h, T, Tp, dtype=torch.float32, device=dev)
-            dS = torch.empty(chunk * h, T, Tp, dtype=torch.bfloat16, device=dev)
+            neg_lse = lse.neg()                                      # the row bias of the ACT_EXP2 epilogue, [B, h, T] f32
+            neg_d = ops.rowdot_heads(dout, out, B, T, h, d, -scale)  # -scale * D: the row bias of ACT_MUL_AUX, what the masked row kernel adds
+        # the pad columns of P and dS, which the K = Tp products read, are zero: the row kernels write them (the causal one also everything
+        # above the diagonal); the fused route's GEMMs write columns < T only and start from zeros
+        P = heads.score_buffer(size, torch.bfloat16, dev, zero_pad=route == "fused")
+        dS = heads.score_buffer(size, torch.bfloat16, dev, zero_pad=route == "fused")
+        S = heads.score_buffer(size, torch.float32, dev) if route == "materialised" else None
+        dP = heads.score_buffer(size, torch.float32, dev) if route != "fused" else None
         st = _s()
-        for b0 in range(0, B, chunk):
-            nb = min(chunk, B - b0)
-            Z = nb * h
-            row0 = b0 * T
-            q_off, k_off, v_off = row0 * ld, row0 * ld + inner, row0 * ld + 2 * inner
-            if fused:
-                # P = exp2(scale log2e Q K^T - lse2) ;  dS = (scale dO V^T - scale D) * P -- both straight out of the GEMM epilogues
-                _gemm(qkv, qkv, P, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale * _LOG2E, act=_lib.ACT_EXP2, batch1=nb, batch0=h,
-                      sA=(T * ld, d), sB=(T * ld, d), sC=(h * T * Tp, T * Tp), a_off=q_off, b_off=k_off, row_bias=neg_lse, row_bias_off=b0 * h * T,
-                      sBias=(h * T, T))
-                _gemm(dout, qkv, dS, lda=inner, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale, act=_lib.ACT_MUL_AUX, aux=P, ld_aux=Tp, batch1=nb,
-                      batch0=h, sA=(T * inner, d), sB=(T * ld, d), sC=(h * T * Tp, T * Tp), a_off=row0 * inner, b_off=v_off, row_bias=neg_d,
-                      row_bias_off=b0 * h * T, sBias=(h * T, T))
-            elif drop:
-                # P = exp2(scale log2e Q K^T - lse2), dPd = dO V^T (f32), then dS = scale P (m dPd - D) and P <- Pd = P m in one row kernel
-                _gemm(qkv, qkv, P, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale * _LOG2E, act=_lib.ACT_EXP2, batch1=nb, batch0=h,
-                      sA=(T * ld, d), sB=(T * ld, d), sC=(h * T * Tp, T * Tp), a_off=q_off, b_off=k_off, row_bias=neg_lse, row_bias_off=b0 * h * T,
-                      sBias=(h * T, T))
-                _gemm(dout, qkv, dP, lda=inner, ldb=ld, ldc=Tp, M=T, N=T, K=d, batch1=nb, batch0=h, sA=(T * inner, d), sB=(T * ld, d),
-                      sC=(h * T * Tp, T * Tp), a_off=row0 * inner, b_off=v_off)
-                softmax_bwd(P.view(-1, Tp)[:Z * T], dP.view(-1, Tp)[:Z * T], neg_d.view(-1)[b0 * h * T:b0 * h * T + Z * T], scale, *ctx.drop,
-                            T=T, row0=b0 * h * T, dS=dS.view(-1, Tp)[:Z * T])
+        for g in heads.chunks(B, size):
+            if route == "materialised":
+                g.scores(g.q(qkv), g.k(qkv), S, alpha=scale)         # S = scale * Q K^T ;  P = softmax(S)
+                check(lib().tribe_softmax_fwd(S.data_ptr(), g.n, T, Tp, P.data_ptr(), Tp, Tp, st), "tribe_softmax_fwd")
+                g.scores(g.o(dout), g.v(qkv), dP)                    # dP = dO V^T ;  dS = P * (dP - rowsum(P dP)) * scale
+                check(lib().tribe_softmax_bwd(P.data_ptr(), dP.data_ptr(), g.n, T, Tp, Tp, Tp, scale, dS.data_ptr(), Tp, st), "tribe_softmax_bwd")
             else:
-                # S = scale * Q K^T ;  P = softmax(S)
-                _gemm(qkv, qkv, S, lda=ld, ldb=ld, ldc=Tp, M=T, N=T, K=d, alpha=scale, batch1=nb, batch0=h, sA=(T * ld, d), sB=(T * ld, d),
-                      sC=(h * T * Tp, T * Tp), a_off=q_off, b_off=k_off)
-                check(lib().tribe_softmax_fwd(S.data_ptr(), Z * T, T, Tp, P.data_ptr(), Tp, Tp, st), "tribe_softmax_fwd")
-                # dP = dO V^T
-                _gemm(dout, qkv, dP, lda=inner, ldb=ld, ldc=Tp, M=T, N=T, K=d, batch1=nb, batch0=h, sA=(T * inner, d), sB=(T * ld, d),
-                      sC=(h * T * Tp, T * Tp), a_off=row0 * inner, b_off=v_off)
-                # dS = P * (dP - rowsum(P dP)) * scale
-                check(lib().tribe_softmax_bwd(P.data_ptr(), dP.data_ptr(), Z * T, T, Tp, Tp, Tp, scale, dS.data_ptr(), Tp, st), "tribe_softmax_bwd")
-            # dQ[q, :] = sum_key dS[q, key] K[key, :]: the reduction runs along the rows of K -> per (b, h) transposed view [d, Tp]
-            kT = _head_transpose(qkv, nb, h, T, d, ld, k_off)
-            _gemm(dS, kT, dqkv, lda=Tp, ldb=Tp, ldc=ld, M=T, N=d, K=Tp, batch1=nb, batch0=h, sA=(h * T * Tp, T * Tp), sB=(h * d * Tp, d * Tp),
-                  sC=(T * ld, d), c_off=q_off)
-            if T % 64 == 0 and d % 8 == 0:
-                # dV[key, :] = sum_q P[q, key] dO[q, :] and dK[key, :] = sum_q dS[q, key] Q[q, :]: both factors have the reduction index q on
-                # their ROWS -- the transposed-operand form of the GEMM (desc.trans_ab) reads P / dS [T, Tp] and the dO / q head slices as
-                # they lie: no P^T, dS^T ([B h, T, T] each), q^T, dO^T
-                _gemm(P, dout, dqkv, lda=Tp, ldb=inner, ldc=ld, M=T, N=d, K=T, batch1=nb, batch0=h, sA=(h * T * Tp, T * Tp), sB=(T * inner, d),
-                      sC=(T * ld, d), b_off=row0 * inner, c_off=v_off, trans_ab=True)
-                _gemm(dS, qkv, dqkv, lda=Tp, ldb=ld, ldc=ld, M=T, N=d, K=T, batch1=nb, batch0=h, sA=(h * T * Tp, T * Tp), sB=(T * ld, d),
-                      sC=(T * ld, d), b_off=q_off, c_off=k_off, trans_ab=True)
+                # P = exp2(scale log2e Q K^T - lse2) straight out of the GEMM epilogue
+                g.scores(g.q(qkv), g.k(qkv), P, alpha=scale * _LOG2E, act=_lib.ACT_EXP2, row_bias=neg_lse)
+                if route == "fused":                                 # dS = (scale dO V^T - scale D) * P, out of the epilogue too
+                    g.scores(g.o(dout), g.v(qkv), dS, alpha=scale, act=_lib.ACT_MUL_AUX, aux=P, row_bias=neg_d)
+                else:   # dPd = dO V^T (f32), then dS = scale P (m dPd - D) and P <- Pd = P m in one row kernel
+                    g.scores(g.o(dout), g.v(qkv), dP)
+                    softmax_bwd(P[:g.n], dP[:g.n], neg_d.view(-1)[g.rows], scale, *ctx.drop, T=T, row0=g.rows.start, dS=dS[:g.n])
+            g.weighted(dS, g.transposed(g.k(qkv)), g.q(dqkv))         # dQ[q, :] = sum_key dS[q, key] K[key, :]
+            # dV[key, :] = sum_q P[q, key] dO[q, :] and dK[key, :] = sum_q dS[q, key] Q[q, :]  (P: Pd on the masked route)
+            if g.reads_transposed:
+                g.weighted_t(P, g.o(dout), g.v(dqkv))
+                g.weighted_t(dS, g.q(qkv), g.k(dqkv))
             else:
-                qT = _head_transpose(qkv, nb, h, T, d, ld, q_off)
-                doT = _head_transpose(dout, nb, h, T, d, inner, row0 * inner)
-                PT = transpose_bf16(P, Z, T, T, T * Tp, Tp)
-                dST = transpose_bf16(dS, Z, T, T, T * Tp, Tp)
-                _gemm(PT, doT, dqkv, lda=Tp, ldb=Tp, ldc=ld, M=T, N=d, K=Tp, batch1=nb, batch0=h, sA=(h * T * Tp, T * Tp), sB=(h * d * Tp, d * Tp),
-                      sC=(T * ld, d), c_off=v_off)
-                _gemm(dST, qT, dqkv, lda=Tp, ldb=Tp, ldc=ld, M=T, N=d, K=Tp, batch1=nb, batch0=h, sA=(h * T * Tp, T * Tp), sB=(h * d * Tp, d * Tp),
-                      sC=(T * ld, d), c_off=k_off)
+                qT, doT = g.transposed(g.q(qkv)), g.transposed(g.o(dout))
+                PT, dST = (transpose_bf16(x, g.nb * h, T, T, T * Tp, Tp) for x in (P, dS))
+                g.weighted(PT, doT, g.v(dqkv))
+                g.weighted(dST, qT, g.k(dqkv))
         if ctx.rotary is not None:   # RotaryAttention: rotate dq, dk back in place -- dqkv is this function's own buffer
             cos, neg_sin, rot_dim, interleaved = ctx.rotary
             ops.rotary_(dqkv, T, h, d, rot_dim, cos, neg_sin, interleaved)
@@ -573,7 +569,7 @@ class Attention(torch.autograd.Function):
 
 class RotaryAttention(torch.autograd.Function):
     """Rotary (in place on the q and k heads of the fused qkv buffer) + attention as ONE node: the backward rotates dq, dk by -theta in the
-    gradient buffer it allocated itself.  As two nodes (Rotary, Attention) the rotation had to work on a clone of the incoming gradient
+    gradient buffer it allocated itself.  As two nodes (a rotary function in front of Attention) the rotation had to work on a clone of the incoming gradient
     (302 MB copied per layer and step at B = 16) and negate the sine table every call.  (p, seed, site): Attention's attention dropout;
     causal: Attention's mask."""
 
@@ -583,7 +579,6 @@ class RotaryAttention(torch.autograd.Function):
         ctx.mark_dirty(qkv)
         ops.rotary_(qkv, T, heads, dim_head, rot_dim, cos, sin, interleaved)
         out = Attention._fwd_any(ctx, qkv, B, T, heads, dim_head, scale, p, seed, site, causal)
-        ctx.meta = (B, T, heads, dim_head, scale)
         ctx.rotary = (cos, neg_sin, rot_dim, interleaved)
         return out, qkv
 
@@ -862,6 +857,3 @@ class PackRows(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         return dy[:, : ctx.k].to(ctx.dtype)
-
-
-_ = tp
