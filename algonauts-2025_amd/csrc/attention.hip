@@ -434,7 +434,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wide384_kernel(const AttnArgs
   }
   // One 1-KiB piece of the K (which = 0) or V (which = 1) tile that starts at key0, into ring slot `slot` of that operand.
   // Round 3: a lone wave per SIMD pays for every LDS-DMA piece with its own issue time, so the piece is as cheap as the ISA allows (the
-  // lesson of the one-wave-per-SIMD GEMM, gemm.hip): SCALAR tile base + the lane's fixed 32-bit byte offset (no 64-bit vector add per
+  // lesson of the one-wave-per-SIMD GEMM, gemm_4wave.hip): SCALAR tile base + the lane's fixed 32-bit byte offset (no 64-bit vector add per
   // piece), M0 written and not saved / restored (nothing else in the kernel uses it).
   const unsigned lds0_u = __builtin_amdgcn_readfirstlane(lds_addr(smem));
   auto stage_piece = [&](int which, int slot, int key0, int i) {
@@ -908,11 +908,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_ksplit384_kernel(const AttnAr
 
 int launch_attn_ksplit384(const AttnArgs& a, int64_t B, hipStream_t s) {
   using C = KSplitCfg;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_ksplit384_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-    attr_done = true;
-  }
+  raise_dynamic_lds_once<attn_fwd_ksplit384_kernel>(C::SMEM);
   const int64_t nblocks = (B * a.heads_q + 7) / 8 * 8 * a.qblocks;
   if (nblocks >= (1ll << 31)) { tribe_set_error("tribe_attention_fwd: grid too large"); return -1; }
   if ((int64_t)a.T * a.ld_kv >= (1ll << 31)) { tribe_set_error("tribe_attention_fwd: sequence too long for 32-bit offsets"); return -1; }
@@ -923,11 +919,7 @@ int launch_attn_ksplit384(const AttnArgs& a, int64_t B, hipStream_t s) {
 
 int launch_attn_wide384(const AttnArgs& a, int64_t B, hipStream_t s) {
   using C = WideCfg;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_wide384_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-    attr_done = true;
-  }
+  raise_dynamic_lds_once<attn_fwd_wide384_kernel>(C::SMEM);
   const int64_t nblocks = (B * a.heads_q + 7) / 8 * 8 * a.qblocks;
   if (nblocks >= (1ll << 31)) { tribe_set_error("tribe_attention_fwd: grid too large"); return -1; }
   if ((int64_t)a.T * a.ld_kv >= (1ll << 31)) { tribe_set_error("tribe_attention_fwd: sequence too long for 32-bit offsets"); return -1; }
@@ -939,11 +931,7 @@ int launch_attn_wide384(const AttnArgs& a, int64_t B, hipStream_t s) {
 template <int DH, int CAUSAL, int RELKEY>
 int launch_attn(const AttnArgs& a, int64_t B, hipStream_t s) {
   using C = AttnCfg<DH>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<DH, CAUSAL, RELKEY>, hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-    attr_done = true;
-  }
+  raise_dynamic_lds_once<attn_fwd_kernel<DH, CAUSAL, RELKEY>>(C::SMEM);
   const int64_t nblocks = (B * a.heads_q + 7) / 8 * 8 * a.qblocks;   // whole groups of 8 (sequence, head) pairs, one per XCD
   if (nblocks >= (1ll << 31)) { tribe_set_error("tribe_attention_fwd: grid too large"); return -1; }
   if ((int64_t)a.T * a.ld_kv >= (1ll << 31)) { tribe_set_error("tribe_attention_fwd: sequence too long for 32-bit offsets"); return -1; }

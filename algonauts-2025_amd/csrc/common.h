@@ -121,6 +121,19 @@ void tribe_set_error(const char* fmt, ...);
 int tribe_internal_prof_before(int role, double flops, hipStream_t s);
 void tribe_internal_prof_after(int slot, hipStream_t s);
 
+// Raises KERNEL's dynamic-LDS limit to `bytes` before a launch that needs more than the default 64 KiB: once per kernel AND device (one
+// process may drive several GPUs, and the attribute is per device); with a device index outside the table the call is made every time.
+template <auto KERNEL>
+static inline void raise_dynamic_lds_once(int bytes) {
+  static bool done[64] = {};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !done[dev]) {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (dev >= 0 && dev < 64) done[dev] = true;
+  }
+}
+
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 
 // grid of a 1-D launch of `total` work items: ceil(total / block), at least 1, capped at max_blocks (the default for the

@@ -1,4 +1,4 @@
-// Pieces shared by the two MFMA GEMM tile configurations (gemm.hip): the operator epilogue and the
+// Pieces shared by the MFMA GEMM kernels (gemm_8wave.h, gemm_128.hip, gemm_4wave.hip, gemm_fp8.hip): the operator epilogue and the
 // XCD-aware tile remap.
 #pragma once
 #include "common.h"
@@ -740,18 +740,12 @@ __device__ __forceinline__ void epilogue_tile16(const tribe_gemm_desc& g, const 
   }
 }
 
-// Host side: one launch of a tile kernel KERNEL(desc, tiles_m, tiles_n, extra...) with SMEM bytes of dynamic LDS.  The dynamic-LDS
-// attribute is set once per kernel AND device (one process may drive several GPUs).
+// Host side: one launch of a tile kernel KERNEL(desc, tiles_m, tiles_n, extra...) with SMEM bytes of dynamic LDS (the limit is raised
+// once per kernel and device: raise_dynamic_lds_once, common.h).
 namespace tribe_gemm_detail {
 template <auto KERNEL, int THREADS, int SMEM, class... Extra>
 static void launch_k(dim3 grid, hipStream_t s, const tribe_gemm_desc* d, int tiles_m, int tiles_n, const Extra&... extra) {
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  raise_dynamic_lds_once<KERNEL>(SMEM);
   hipLaunchKernelGGL(KERNEL, grid, dim3(THREADS, 1, 1), SMEM, s, *d, tiles_m, tiles_n, extra...);
 }
 }  // namespace tribe_gemm_detail

@@ -2,7 +2,7 @@
 // the product of the two per-tensor quantisation scales (BASELINE config 5: "fp8 MFMA extractor GEMMs").
 //
 // Same 256 x 256 tile, 8-wave 2x4 layout, 2-buffer LDS-DMA pipeline with counted vmcnt and staggered wave groups as the bf16
-// kernel in gemm.hip -- a K-tile of 128 e4m3 values is the SAME 128-byte-per-row LDS image as 64 bf16 values, so staging,
+// kernel in gemm_8wave.h -- a K-tile of 128 e4m3 values is the SAME 128-byte-per-row LDS image as 64 bf16 values, so staging,
 // swizzle and barriers are byte-identical.  What changes is the matrix instruction: one
 // v_mfma_scale_f32_16x16x128_f8f6f4 (unit E8M0 scales, formats 0 = e4m3) per 16 x 16 x 128 step instead of two
 // v_mfma_f32_16x16x32_bf16 per 16 x 16 x 64: 4x the K per instruction at 2x the cycles = 2x the bf16 rate

@@ -9,7 +9,7 @@
 
 void tribe_set_error(const char* fmt, ...);
 
-// The stream-K schedule the transposed-operand kernel takes by value (gemm.hip wraps it as its kernel-parameter type SkSched; the
+// The stream-K schedule the transposed-operand kernel takes by value (gemm_8wave.h wraps it as its kernel-parameter type SkSched; the
 // schedule itself is described there).
 struct SkSchedule {
   int tiles_dp;   // tiles (linear index < tiles_dp) computed whole; >= tiles_m * tiles_n: no stream-K
@@ -27,7 +27,7 @@ constexpr int K_STEP = 64;        // BK of every bf16 kernel
 constexpr int K_STEP_FP8 = 128;
 enum { KIND_SMALL = 0, KIND_BIG = 1, KIND_RING = 2, KIND_BIG4W = 3 };
 // (kernel symbol, output is bf16, role template argument) of every pair that exists as a kernel; every other (dtype, role) combination
-// runs under the GENERIC symbol of its dtype.  The launch tables of gemm.hip and the enum below are generated from this list.
+// runs under the GENERIC symbol of its dtype.  The launch tables (gemm_launch.h) and the enum below are generated from this list.
 #define TRIBE_GEMM_PAIRS(X)                                                                                            \
   X(PAIR_GENERIC_BF16, 1, TRIBE_ROLE_GENERIC) X(PAIR_GENERIC_F32, 0, TRIBE_ROLE_GENERIC)                               \
   X(PAIR_EXT_BF16, 1, TRIBE_ROLE_EXT) X(PAIR_EXT_F32, 0, TRIBE_ROLE_EXT)                                               \

@@ -8,4 +8,4 @@ for f in attention attention_d64; do
   /opt/rocm/bin/hipcc -O3 -fPIC -std=c++17 --offload-arch=gfx950 -DTRIBE_ATTN_STAMPS -c $f.hip -o ../../ab_tmp/${f}_stamps.o
 done
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 ../../ab_tmp/attention_stamps.o ../../ab_tmp/attention_d64_stamps.o \
-  gemm.o elementwise.o loss.o encoder.o extractors.o backward.o features.o gemm_fp8.o abi.o -o ../../ab_tmp/libtribe_hip_attn_stamps.so
+  $(ls *.o | grep -v -x -e attention.o -e attention_d64.o) -o ../../ab_tmp/libtribe_hip_attn_stamps.so   # every other object as make left it

@@ -1,10 +1,14 @@
-"""Audit of the attention and GEMM kernels' ISA (run after every edit of attention*.hip / gemm.hip; CPU only, needs hipcc).  DH = 384:
+"""Audit of the attention and GEMM kernels' ISA (run after every edit of attention*.hip / gemm_8wave.h; CPU only, needs hipcc).  DH = 384:
   * no scratch (a spilled Q fragment reloads every tile),
   * no compiler-generated v_accvgpr_* or MFMA outside the ASMSTART / ASMEND blocks (a0..a191 hold O^T and belong to the asm
     statements of attn_acc_regs.h; the compiler must not allocate accumulator registers of its own),
   * prints the register budget and the instruction mix of the key loop.
-Usage: python scripts/check_attn_wide_isa.py [--no-gemm | --attention-only | --gemm4w-isa FILE.s]
-(--attention-only: attention.hip alone -- the Makefile runs this after compiling attention.o and fails the build on a violation.)"""
+Usage: python scripts/check_attn_wide_isa.py [--no-gemm | --attention-only | --attention-isa FILE.s | --gemm4w-isa FILE.s]
+Without a FILE.s the script compiles the sources itself (--attention-only: attention.hip alone; --no-gemm: without the 8-wave GEMM unit),
+with the compiler of HIPCC and the architecture of ARCH in the environment (defaults /opt/rocm/bin/hipcc, gfx950).  The two FILE.s modes
+audit the device assembly of a compilation that already ran: the Makefile hands them the -save-temps output of the very compilations
+whose objects it links (attention.o, gemm_4wave.o) and fails the build on a violation."""
+import os
 import re
 import subprocess
 import sys
@@ -12,16 +16,19 @@ import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+ARCH = os.environ.get("ARCH", "gfx950")
+GEMM_8WAVE = "gemm_8wave_nb4.hip"   # the unit that instantiates gemm_nt_256x256x64 at 256 x 256 (both forms)
 CSRC = ROOT / "algonauts-2025_amd" / "csrc"
 
 
 def device_isa(sources: list[str]) -> dict[str, str]:
-    """gfx950 assembly of each source, the compilations running side by side (device side only)."""
+    """Device assembly of each source, the compilations running side by side (device side only)."""
     with tempfile.TemporaryDirectory() as tmp:
         procs = []
         for src in sources:
             out = Path(tmp, src.replace(".hip", ".s"))
-            procs.append((src, out, subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S",
+            procs.append((src, out, subprocess.Popen([HIPCC, "-O3", "-std=c++17", f"--offload-arch={ARCH}", "--cuda-device-only", "-S",
                                                       f"-I{CSRC}", f"-I{ROOT / 'include'}", str(CSRC / src), "-o", str(out)],
                                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=tmp)))
         isa = {}
@@ -34,7 +41,7 @@ def device_isa(sources: list[str]) -> dict[str, str]:
 
 
 def audit_gemm4w(isa_text: str) -> bool:
-    """The one-wave-per-SIMD GEMM kernel (gemm.hip part 3) keeps 64 accumulators in compiler-allocated AGPRs behind "+a" operands of inline-asm
+    """The one-wave-per-SIMD GEMM kernel (gemm_4wave.hip) keeps 64 accumulators in compiler-allocated AGPRs behind "+a" operands of inline-asm
     MFMAs: it must compile without scratch, with all 256 AGPRs, and between the first and the last MFMA of a kernel the compiler must
     neither move accumulators (v_accvgpr_*) nor touch scratch."""
     good = True
@@ -67,14 +74,18 @@ def audit_gemm4w(isa_text: str) -> bool:
     return good
 
 
-if "--gemm4w-isa" in sys.argv[1:]:   # audit a compiled ISA file (the Makefile passes the -save-temps output of gemm.hip part 3)
+if "--gemm4w-isa" in sys.argv[1:]:   # audit a compiled ISA file (the Makefile passes the -save-temps output of gemm_4wave.hip)
     ok4 = audit_gemm4w(Path(sys.argv[sys.argv.index("--gemm4w-isa") + 1]).read_text())
     print("OK: one-wave-per-SIMD GEMM kernels keep their accumulators in place" if ok4 else "gemm4w audit FAILED")
     sys.exit(0 if ok4 else 1)
 
-ATTN_ONLY = "--attention-only" in sys.argv[1:]
-WITH_GEMM = "--no-gemm" not in sys.argv[1:] and not ATTN_ONLY   # gemm.hip takes two minutes to compile (its role instantiations); the unit test skips it
-ISA = device_isa(["attention.hip"] + ([] if ATTN_ONLY else ["attention_d64.hip"]) + (["gemm.hip"] if WITH_GEMM else []))
+ATTN_ISA = sys.argv[sys.argv.index("--attention-isa") + 1] if "--attention-isa" in sys.argv[1:] else None
+ATTN_ONLY = "--attention-only" in sys.argv[1:] or ATTN_ISA is not None
+WITH_GEMM = "--no-gemm" not in sys.argv[1:] and not ATTN_ONLY   # the 8-wave unit takes two minutes to compile (its role instantiations); the unit test skips it
+if ATTN_ISA is not None:
+    ISA = {"attention.hip": Path(ATTN_ISA).read_text()}
+else:
+    ISA = device_isa(["attention.hip"] + ([] if ATTN_ONLY else ["attention_d64.hip"]) + ([GEMM_8WAVE] if WITH_GEMM else []))
 text = ISA["attention.hip"]
 def audit(kernel: str, max_regs: int) -> bool:
     m = re.search(rf"^(_ZN\S*{kernel}\S*):.*?\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M)
@@ -127,7 +138,7 @@ def no_scratch(source: str, kernels: list[str]) -> bool:
 if not ATTN_ONLY:
     ok &= no_scratch("attention_d64.hip", ["attn_fwd_d64_kernel", "attn_fwd_d64_pair_kernel"])
 if WITH_GEMM:
-    ok &= no_scratch("gemm.hip", ["gemm_nt_256x256x64"])
+    ok &= no_scratch(GEMM_8WAVE, ["gemm_nt_256x256x64"])
 if not ok:
     sys.exit(1)
 print("OK: no scratch, no compiler accumulator-register traffic")

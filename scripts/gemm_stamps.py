@@ -1,4 +1,4 @@
-"""Diagnostic: libtribe_hip_stamps.so = the library with -DTRIBE_GEMM_STAMPS in the 8-wave 256 x 256 GEMM (part 0 of gemm.hip; every
+"""Diagnostic: libtribe_hip_stamps.so = the library with -DTRIBE_GEMM_STAMPS in the 8-wave 256 x 256 GEMM (gemm_8wave_nb4.hip; every
 other object as `make` left it in csrc/).  Prints, for the four encoder GEMMs at their B = 64 shapes and with their model operators,
 where a wave's time goes: the K loop by slot (shares), and per tile the cycles from kernel entry to the first K-loop iteration, from
 the loop's end to the last store issued, and to the last store retired (wave end) -- once through the role-compiled epilogue and once
@@ -14,13 +14,13 @@ ROOT = Path(__file__).resolve().parent.parent
 CS = ROOT / "algonauts-2025_amd" / "csrc"
 out = ROOT / "ab_tmp" / "libtribe_hip_stamps.so"
 out.parent.mkdir(exist_ok=True)
-srcs = [CS / "gemm.hip", CS / "gemm_common.h", CS / "common.h", ROOT / "include" / "tribe_hip.h"]
+srcs = [CS / "gemm_8wave_nb4.hip", CS / "gemm_8wave.h", CS / "gemm_launch.h", CS / "gemm_common.h", CS / "common.h", ROOT / "include" / "tribe_hip.h"]
 if not out.exists() or out.stat().st_mtime < max(s.stat().st_mtime for s in srcs):
-    others = sorted(o for o in CS.glob("*.o") if o.name != "gemm.o")
-    assert any(o.name == "gemm_p1.o" for o in others), "run `make` in csrc/ first: the other objects are linked as they are"
+    others = sorted(o for o in CS.glob("*.o") if o.name != "gemm_8wave_nb4.o")
+    assert any(o.name == "gemm_8wave_nb3.o" for o in others), "run `make` in csrc/ first: the other objects are linked as they are"
     obj = out.parent / "gemm_stamps.o"
     hipcc = ["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950"]
-    subprocess.run([*hipcc, "-DTRIBE_GEMM_PART=0", "-DTRIBE_GEMM_STAMPS", "-c", str(CS / "gemm.hip"), "-o", str(obj)], check=True)
+    subprocess.run([*hipcc, "-DTRIBE_GEMM_STAMPS", "-c", str(CS / "gemm_8wave_nb4.hip"), "-o", str(obj)], check=True)
     subprocess.run([*hipcc[:1], "-shared", "-fPIC", "--offload-arch=gfx950", str(obj), *map(str, others), "-o", str(out)], check=True)
 if "--build-only" in sys.argv:
     sys.exit(0)

@@ -75,7 +75,7 @@ def test_argument_errors_do_not_need_a_gpu():
 
 @pytest.mark.parametrize("tiles,nk", [(576, 256), (64, 256), (120, 136), (6, 344), (272, 128), (144, 256), (432, 256), (4, 2), (300, 9), (257, 64)])
 def test_stream_k_schedule_covers_every_k_step_once(tiles, nk):
-    """tribe_gemm_stream_k_plan is the schedule the weight-gradient kernel decodes from blockIdx (csrc/gemm.hip, SkSched).  The decode is
+    """tribe_gemm_stream_k_plan is the schedule the weight-gradient kernel decodes from blockIdx (csrc/gemm_8wave.h, SkSched).  The decode is
     replayed here: every K-step of every tile must be covered exactly once, whole tiles by one workgroup, split tiles by parts that the
     reduce kernel finds under the slots it computes, and the second parts must be queued longest first."""
     from tribe_hip import _lib
