@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "philox.h"
+#include "row_wave.h"
 #include "softmax_row.h"
 
 namespace {
@@ -264,11 +265,12 @@ template <bool CAUSAL>
 void launch_fwd(bool vec, bool reg, hipStream_t st, const float* S, uint16_t* Pd, float* lse, int64_t rows, int64_t T, int64_t T_pad, int64_t ld_s,
                 int64_t ld_p, int64_t row0, mask_key k) {
   const dim3 grid((unsigned)((rows + 3) / 4));
-  if (reg && T == 256) hipLaunchKernelGGL((softmax_rows_reg_kernel<1, CAUSAL>), grid, dim3(256), 0, st, S, rows, ld_s, Pd, ld_p, lse, row0, k);
-  else if (reg && T == 512) hipLaunchKernelGGL((softmax_rows_reg_kernel<2, CAUSAL>), grid, dim3(256), 0, st, S, rows, ld_s, Pd, ld_p, lse, row0, k);
-  else if (reg && T == 1024) hipLaunchKernelGGL((softmax_rows_reg_kernel<4, CAUSAL>), grid, dim3(256), 0, st, S, rows, ld_s, Pd, ld_p, lse, row0, k);
-  else if (reg && T == 2048) hipLaunchKernelGGL((softmax_rows_reg_kernel<8, CAUSAL>), grid, dim3(256), 0, st, S, rows, ld_s, Pd, ld_p, lse, row0, k);
-  else if (vec) hipLaunchKernelGGL((softmax_rows_walk_kernel<true, CAUSAL>), grid, dim3(256), 0, st, S, rows, T, ld_s, Pd, T_pad, ld_p, lse, row0, k);
+  // NV: vec, T_pad == T and T = 256 / 512 / 1024 / 2048 -> the row in 1 / 2 / 4 / 8 float4 per lane; else a walk, 16 bytes at a time if vec
+  if (reg && first_nv<1, 2, 4, 8>([&](int nv) { return T == 256 * nv; }, [&](auto nv) {
+        hipLaunchKernelGGL((softmax_rows_reg_kernel<decltype(nv)::value, CAUSAL>), grid, dim3(256), 0, st, S, rows, ld_s, Pd, ld_p, lse, row0, k);
+      }))
+    return;
+  if (vec) hipLaunchKernelGGL((softmax_rows_walk_kernel<true, CAUSAL>), grid, dim3(256), 0, st, S, rows, T, ld_s, Pd, T_pad, ld_p, lse, row0, k);
   else hipLaunchKernelGGL((softmax_rows_walk_kernel<false, CAUSAL>), grid, dim3(256), 0, st, S, rows, T, ld_s, Pd, T_pad, ld_p, lse, row0, k);
 }
 

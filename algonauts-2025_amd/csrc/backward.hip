@@ -2,6 +2,7 @@
 // the dense gradients are MFMA GEMMs (gemm.hip) fed with transposed bf16 operands produced here.  Roofline: HBM.  The gradient of the MSE loss (tribe_mse_bwd) is with the other
 // element-wise losses in robust_loss.hip.
 #include "common.h"
+#include "row_wave.h"
 
 namespace {
 
@@ -655,22 +656,17 @@ static int scalenorm_bwd_launch(const float* x, const void* dy, int32_t dy_dtype
   TRIBE_REQUIRE(dy_dtype == TRIBE_F32 || dy_dtype == TRIBE_BF16, "tribe_scalenorm_bwd: dy dtype must be f32 or bf16");
   hipStream_t s = (hipStream_t)stream;
   const bool aligned = (((uintptr_t)x | (uintptr_t)dx | (uintptr_t)(dres ? dres : x) | (uintptr_t)(rs ? rs : x)) % 16) == 0 && ((uintptr_t)dy % 16) == 0;
-#define TRIBE_SNB(NV)                                                                                                             \
-  do {                                                                                                                            \
-    if (dy_dtype == TRIBE_F32)                                                                                                    \
-      hipLaunchKernelGGL((scalenorm_bwd_reg_kernel<float, NV>), grid, dim3(256), 0, s, x, (const float*)dy, g, gain_scale, eps, rows, dres, rs, dx, dg, dg_rows); \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((scalenorm_bwd_reg_kernel<unsigned short, NV>), grid, dim3(256), 0, s, x, (const unsigned short*)dy, g, gain_scale, eps, \
-                         rows, dres, rs, dx, dg, dg_rows);                                                                               \
-  } while (0)
-  if (aligned && dim == 3072) TRIBE_SNB(12);
-  else if (aligned && dim == 768) TRIBE_SNB(3);
-  else if (dy_dtype == TRIBE_F32)
-    hipLaunchKernelGGL(scalenorm_bwd_kernel<float>, grid, dim3(256), 0, s, x, (const float*)dy, g, gain_scale, eps, rows, dim, dres, rs, dx, dg, dg_rows);
-  else
-    hipLaunchKernelGGL(scalenorm_bwd_kernel<unsigned short>, grid, dim3(256), 0, s, x, (const unsigned short*)dy, g, gain_scale, eps, rows,
-                       dim, dres, rs, dx, dg, dg_rows);
-#undef TRIBE_SNB
+  // NV: x, dx, dres, rs, dy 16-byte aligned and dim = 3072 / 768 -> scalenorm_bwd_reg_kernel with the rows in 12 / 3 float4 per lane; else the
+  // element walk of scalenorm_bwd_kernel (1024 included)
+  const bool f32 = dy_dtype == TRIBE_F32;
+  if (!(aligned && first_nv<12, 3>([&](int nv) { return dim == 256 * nv; }, [&](auto nv) {
+          constexpr int NV = decltype(nv)::value;
+          if (f32) hipLaunchKernelGGL((scalenorm_bwd_reg_kernel<float, NV>), grid, dim3(256), 0, s, x, (const float*)dy, g, gain_scale, eps, rows, dres, rs, dx, dg, dg_rows);
+          else hipLaunchKernelGGL((scalenorm_bwd_reg_kernel<unsigned short, NV>), grid, dim3(256), 0, s, x, (const unsigned short*)dy, g, gain_scale, eps, rows, dres, rs, dx, dg, dg_rows);
+        }))) {
+    if (f32) hipLaunchKernelGGL(scalenorm_bwd_kernel<float>, grid, dim3(256), 0, s, x, (const float*)dy, g, gain_scale, eps, rows, dim, dres, rs, dx, dg, dg_rows);
+    else hipLaunchKernelGGL(scalenorm_bwd_kernel<unsigned short>, grid, dim3(256), 0, s, x, (const unsigned short*)dy, g, gain_scale, eps, rows, dim, dres, rs, dx, dg, dg_rows);
+  }
   TRIBE_LAUNCH_CHECK();
   if (dg_rows) {
     hipLaunchKernelGGL(scalenorm_dg_sum_kernel, dim3(1), dim3(1024), 0, s, (const float*)dg_rows, rows, dg);
@@ -699,11 +695,11 @@ extern "C" int tribe_softmax_bwd(const uint16_t* P, const float* dP, int64_t row
   hipStream_t st = (hipStream_t)stream;
   const bool reg = T_pad == T && T % 256 == 0 && T <= 2048 && ld_p % 4 == 0 && ld_dp % 4 == 0 && ld_ds % 4 == 0 && ((uintptr_t)P % 8) == 0 &&
                    ((uintptr_t)dP % 16) == 0 && ((uintptr_t)dS % 8) == 0;
-  if (reg && T == 256) hipLaunchKernelGGL(softmax_bwd_reg_kernel<1>, grid, dim3(256), 0, st, P, dP, rows, ld_p, ld_dp, scale, dS, ld_ds);
-  else if (reg && T == 512) hipLaunchKernelGGL(softmax_bwd_reg_kernel<2>, grid, dim3(256), 0, st, P, dP, rows, ld_p, ld_dp, scale, dS, ld_ds);
-  else if (reg && T == 1024) hipLaunchKernelGGL(softmax_bwd_reg_kernel<4>, grid, dim3(256), 0, st, P, dP, rows, ld_p, ld_dp, scale, dS, ld_ds);
-  else if (reg && T == 2048) hipLaunchKernelGGL(softmax_bwd_reg_kernel<8>, grid, dim3(256), 0, st, P, dP, rows, ld_p, ld_dp, scale, dS, ld_ds);
-  else hipLaunchKernelGGL(softmax_bwd_kernel, grid, dim3(256), 0, st, P, dP, rows, T, T_pad, ld_p, ld_dp, scale, dS, ld_ds);
+  // NV: T_pad == T, T = 256 / 512 / 1024 / 2048, the pitches multiples of 4, P and dS 8-byte and dP 16-byte aligned -> the row in 1 / 2 / 4 / 8 float4 per lane
+  if (!(reg && first_nv<1, 2, 4, 8>([&](int nv) { return T == 256 * nv; }, [&](auto nv) {
+          hipLaunchKernelGGL(softmax_bwd_reg_kernel<decltype(nv)::value>, grid, dim3(256), 0, st, P, dP, rows, ld_p, ld_dp, scale, dS, ld_ds);
+        })))
+    hipLaunchKernelGGL(softmax_bwd_kernel, grid, dim3(256), 0, st, P, dP, rows, T, T_pad, ld_p, ld_dp, scale, dS, ld_ds);
   TRIBE_LAUNCH_CHECK();
   return 0;
 }

@@ -2,7 +2,10 @@
 // rotary, softmax, V transpose, adaptive average pool.  All are pure streaming
 // kernels (roofline: HBM bandwidth); loads/stores are 8-16 B per lane where the
 // layout allows.
+// The norms (scalenorm_kernel<OUT, NV>, rowstat_norm_kernel<OUT, LN, NV>) are one template each over row_wave.h:
+// NV > 0 keeps the row in registers, NV == 0 walks it once per pass.
 #include "common.h"
+#include "row_wave.h"
 #include "softmax_row.h"
 
 namespace {
@@ -100,65 +103,28 @@ __global__ __launch_bounds__(256) void transpose_cast_kernel(const T* __restrict
 // ---------------------------------------------------------------------------------
 // ScaleNorm: one wave per row;  y = x * (gain / max(||x||, eps))
 // ---------------------------------------------------------------------------------
-template <int OUT_BF16>
-__global__ __launch_bounds__(256) void scalenorm_kernel(const float* __restrict__ x, int64_t rows, int64_t dim,
+// NV > 0 holds the row in registers between the reduction and the scaling (dim = 256 * NV, NV float4 per lane; `dim` is not read):
+// one HBM read of x instead of two -- the counters showed the second touch of the two-pass walk (NV == 0) mostly missing L2
+// (1.61 GB fetched for a 0.81 GB input) -- and all NV loads of a row in flight at once.
+template <int OUT_BF16, int NV>
+__global__ __launch_bounds__(256) void scalenorm_kernel(const float* __restrict__ x, int64_t rows, int64_t dim_arg,
                                                         const float* __restrict__ g, float gain_scale, float eps,
                                                         void* __restrict__ y) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float4* xr = (const float4*)(x + row * dim);
-  const int64_t n4 = dim >> 2;
+  const int64_t dim = NV > 0 ? 256 * NV : dim_arg;
+  const float* xr = x + row * dim;
+  float4 v[NV > 0 ? NV : 1];
+  quads_load<NV, true>(xr, v, dim, lane);
   float ss = 0.f;
-  for (int64_t i = lane; i < n4; i += 64) {
-    const float4 v = xr[i];
-    ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-  }
+  quads_each<NV, true>(xr, v, dim, lane, [&](auto, const float4& a, int) { ss += dot4(a, a); });
   ss = wave_sum(ss);
   const float scale = (g[0] * gain_scale) / fmaxf(sqrtf(ss), eps);
-  for (int64_t i = lane; i < n4; i += 64) {
-    const float4 v = xr[i];  // second touch is an L2 hit (12 KiB row)
-    if (OUT_BF16) {
-      u16x4_t o;
-      o[0] = f32_to_bf16(v.x * scale); o[1] = f32_to_bf16(v.y * scale);
-      o[2] = f32_to_bf16(v.z * scale); o[3] = f32_to_bf16(v.w * scale);
-      ((u16x4_t*)((unsigned short*)y + row * dim))[i] = o;
-    } else {
-      ((float4*)((float*)y + row * dim))[i] = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
-    }
-  }
-}
-
-// Same, with the row held in registers between the reduction and the scaling (dim = 256 * NV, NV float4 per lane): one
-// HBM read of x instead of two -- the counters showed the second touch of the two-pass kernel mostly missing L2
-// (1.61 GB fetched for a 0.81 GB input) -- and all NV loads of a row in flight at once.
-template <int OUT_BF16, int NV>
-__global__ __launch_bounds__(256) void scalenorm_reg_kernel(const float* __restrict__ x, int64_t rows, const float* __restrict__ g,
-                                                            float gain_scale, float eps, void* __restrict__ y) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  constexpr int64_t dim = 256 * NV;
-  const float4* xr = (const float4*)(x + row * dim);
-  float4 v[NV];
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = xr[lane + 64 * k];
-  float ss = 0.f;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) ss += v[k].x * v[k].x + v[k].y * v[k].y + v[k].z * v[k].z + v[k].w * v[k].w;
-  ss = wave_sum(ss);
-  const float scale = (g[0] * gain_scale) / fmaxf(sqrtf(ss), eps);
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    if (OUT_BF16) {
-      u16x4_t o;
-      o[0] = f32_to_bf16(v[k].x * scale); o[1] = f32_to_bf16(v[k].y * scale);
-      o[2] = f32_to_bf16(v[k].z * scale); o[3] = f32_to_bf16(v[k].w * scale);
-      ((u16x4_t*)((unsigned short*)y + row * dim))[lane + 64 * k] = o;
-    } else {
-      ((float4*)((float*)y + row * dim))[lane + 64 * k] = make_float4(v[k].x * scale, v[k].y * scale, v[k].z * scale, v[k].w * scale);
-    }
-  }
+  void* yr = out_row<OUT_BF16>(y, row, dim);
+  quads_each<NV, true>(xr, v, dim, lane, [&](auto q, const float4& a, int) {   // a walk's second touch is an L2 hit (12 KiB row)
+    store4<OUT_BF16>(yr, q, make_float4(a.x * scale, a.y * scale, a.z * scale, a.w * scale));
+  });
 }
 
 // ---------------------------------------------------------------------------------
@@ -223,145 +189,65 @@ __global__ __launch_bounds__(256) void rotary_kernel(unsigned short* __restrict_
 // RMSNorm / LayerNorm: one wave per row (f32 in, f32 statistics), bf16 or f32 out; OUT_BF16 == 2: e4m3 bytes of the
 // bf16-rounded result times q_inv_scale, saturating, NaN passed through (= the bf16 norm followed by tribe_quantize_fp8_fwd, bit for bit, in one pass)
 // ---------------------------------------------------------------------------------
-template <int OUT_BF16, int LAYERNORM>
+// NV > 0 holds the row in registers (NV float4 per lane, dim <= 256 * NV): x is read from memory ONCE instead of the three times of the
+// walk (NV == 0: statistics, centred variance, output).  Same per-lane accumulation order, so the two forms give the same bits.
+template <int OUT_BF16, int LAYERNORM, int NV>
 __global__ __launch_bounds__(256) void rowstat_norm_kernel(const float* __restrict__ x, int64_t rows, int64_t dim,
                                                            const float* __restrict__ w, const float* __restrict__ b, float eps,
                                                            void* __restrict__ y, float q_inv_scale = 0.f) {
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float4* xr = (const float4*)(x + row * dim);
-  const int64_t n4 = dim >> 2;
+  const float* xr = x + row * dim;
+  float4 v[NV > 0 ? NV : 1];
+  quads_load<NV>(xr, v, dim, lane);
   float s1 = 0.f, s2 = 0.f;
-  for (int64_t i = lane; i < n4; i += 64) {
-    const float4 v = xr[i];
-    s1 += v.x + v.y + v.z + v.w;
-    s2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-  }
+  quads_each<NV>(xr, v, dim, lane, [&](auto, const float4& a, int) {
+    s1 += a.x + a.y + a.z + a.w;
+    s2 += dot4(a, a);
+  });
   s1 = wave_sum(s1);
   s2 = wave_sum(s2);
   float mean = 0.f, rstd;
   if (LAYERNORM) {
     mean = s1 / (float)dim;
-    float var = 0.f;  // second pass for the centred variance (row is L2-resident)
-    for (int64_t i = lane; i < n4; i += 64) {
-      const float4 v = xr[i];
-      const float a = v.x - mean, c = v.y - mean, d = v.z - mean, e = v.w - mean;
-      var += a * a + c * c + d * d + e * e;
-    }
+    float var = 0.f;  // second pass for the centred variance (a walk finds the row in L2)
+    quads_each<NV>(xr, v, dim, lane, [&](auto, const float4& a, int) {
+      const float4 d = make_float4(a.x - mean, a.y - mean, a.z - mean, a.w - mean);
+      var += dot4(d, d);
+    });
     var = wave_sum(var) / (float)dim;
     rstd = rsqrtf(var + eps);
+    // the output pass subtracts the mean again: seen as the same value, hipcc keeps the centred row of the pass above in registers
+    // next to the row itself (20 VGPRs more at NV = 12, an occupancy step)
+    asm volatile("" : "+v"(mean));
   } else {
     rstd = rsqrtf(s2 / (float)dim + eps);
   }
-  for (int64_t i = lane; i < n4; i += 64) {
-    const float4 v = xr[i];
-    const float4 g = ((const float4*)w)[i];
-    float o0 = (v.x - mean) * rstd * g.x, o1 = (v.y - mean) * rstd * g.y, o2 = (v.z - mean) * rstd * g.z, o3 = (v.w - mean) * rstd * g.w;
+  void* yr = out_row<OUT_BF16>(y, row, dim);
+  quads_each<NV>(xr, v, dim, lane, [&](auto q, const float4& a, int) {
+    const float4 g = load4(w, q);
+    float4 o = make_float4((a.x - mean) * rstd * g.x, (a.y - mean) * rstd * g.y, (a.z - mean) * rstd * g.z, (a.w - mean) * rstd * g.w);
     if (LAYERNORM && b) {
-      const float4 bb = ((const float4*)b)[i];
-      o0 += bb.x; o1 += bb.y; o2 += bb.z; o3 += bb.w;
+      const float4 bb = load4(b, q);
+      o.x += bb.x; o.y += bb.y; o.z += bb.z; o.w += bb.w;
     }
-    if (OUT_BF16 == 2) {
-      float q[4] = {o0, o1, o2, o3};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) q[j] = bf16_to_f32(f32_to_bf16(q[j])) * q_inv_scale;
-      ((int*)((unsigned char*)y + row * dim))[i] = pack_e4m3x4(q[0], q[1], q[2], q[3]);
-    } else if (OUT_BF16) {
-      u16x4_t o;
-      o[0] = f32_to_bf16(o0); o[1] = f32_to_bf16(o1); o[2] = f32_to_bf16(o2); o[3] = f32_to_bf16(o3);
-      ((u16x4_t*)((unsigned short*)y + row * dim))[i] = o;
-    } else {
-      ((float4*)((float*)y + row * dim))[i] = make_float4(o0, o1, o2, o3);
-    }
-  }
+    store4<OUT_BF16>(yr, q, o, q_inv_scale);
+  });
 }
 
-// The same norm with the row held in registers (NV float4 per lane, dim <= 256 * NV): x is read from memory ONCE instead of three
-// times (statistics, centred variance, output); same per-lane accumulation order, so the results are bit-identical to the kernel above.
-template <int OUT_BF16, int LAYERNORM, int NV>
-__global__ __launch_bounds__(256) void rowstat_norm_reg_kernel(const float* __restrict__ x, int64_t rows, int64_t dim,
-                                                               const float* __restrict__ w, const float* __restrict__ b, float eps,
-                                                               void* __restrict__ y, float q_inv_scale = 0.f) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float4* xr = (const float4*)(x + row * dim);
-  const int n4 = (int)(dim >> 2);
-  float4 v[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int i = lane + 64 * j;
-    v[j] = i < n4 ? xr[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    if (lane + 64 * j < n4) {
-      s1 += v[j].x + v[j].y + v[j].z + v[j].w;
-      s2 += v[j].x * v[j].x + v[j].y * v[j].y + v[j].z * v[j].z + v[j].w * v[j].w;
-    }
-  }
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  float mean = 0.f, rstd;
-  if (LAYERNORM) {
-    mean = s1 / (float)dim;
-    float var = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      if (lane + 64 * j < n4) {
-        const float a = v[j].x - mean, c = v[j].y - mean, d = v[j].z - mean, e = v[j].w - mean;
-        var += a * a + c * c + d * d + e * e;
-      }
-    }
-    var = wave_sum(var) / (float)dim;
-    rstd = rsqrtf(var + eps);
-  } else {
-    rstd = rsqrtf(s2 / (float)dim + eps);
-  }
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int i = lane + 64 * j;
-    if (i >= n4) continue;
-    const float4 g = ((const float4*)w)[i];
-    float o0 = (v[j].x - mean) * rstd * g.x, o1 = (v[j].y - mean) * rstd * g.y, o2 = (v[j].z - mean) * rstd * g.z, o3 = (v[j].w - mean) * rstd * g.w;
-    if (LAYERNORM && b) {
-      const float4 bb = ((const float4*)b)[i];
-      o0 += bb.x; o1 += bb.y; o2 += bb.z; o3 += bb.w;
-    }
-    if (OUT_BF16 == 2) {
-      float q[4] = {o0, o1, o2, o3};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) q[k] = bf16_to_f32(f32_to_bf16(q[k])) * q_inv_scale;
-      ((int*)((unsigned char*)y + row * dim))[i] = pack_e4m3x4(q[0], q[1], q[2], q[3]);
-    } else if (OUT_BF16) {
-      u16x4_t o;
-      o[0] = f32_to_bf16(o0); o[1] = f32_to_bf16(o1); o[2] = f32_to_bf16(o2); o[3] = f32_to_bf16(o3);
-      ((u16x4_t*)((unsigned short*)y + row * dim))[i] = o;
-    } else {
-      ((float4*)((float*)y + row * dim))[i] = make_float4(o0, o1, o2, o3);
-    }
-  }
-}
-
-// launch the register-resident form when the row fits 12 float4 per lane (dim <= 3072) and is 16-byte aligned, else the three-pass walk
+// NV: x, w, b 16-byte aligned, y aligned to its float4 / u16x4 / packed fp8x4 store (16 / 8 / 4 bytes for OUT 0 / 1 / 2; row pitch = dim
+// elements), dim % 4 == 0 and ceil(dim / 256) <= 4 / 6 / 8 / 12 -> the row in 4 / 6 / 8 / 12 float4 per lane; else 0, the three-pass walk
 template <int OUT_BF16, int LAYERNORM>
 void launch_rowstat_norm(const float* x, int64_t rows, int64_t dim, const float* w, const float* b, float eps, void* y, float q_inv_scale,
                          hipStream_t s) {
   dim3 grid((unsigned)((rows + 3) / 4));
-  const int nv = (int)((dim / 4 + 63) / 64);
-  // the register-resident kernel stores float4 / u16x4 / packed fp8x4 per lane: y needs 16 / 8 / 4-byte alignment (row pitch = dim elements)
   const uintptr_t y_align = OUT_BF16 == 0 ? 16 : (OUT_BF16 == 1 ? 8 : 4);
   const bool aligned = ((uintptr_t)x % 16) == 0 && ((uintptr_t)w % 16) == 0 && (!b || ((uintptr_t)b % 16) == 0) && ((uintptr_t)y % y_align) == 0 &&
                        dim % 4 == 0;
-#define TRIBE_RSN(NV) hipLaunchKernelGGL((rowstat_norm_reg_kernel<OUT_BF16, LAYERNORM, NV>), grid, dim3(256), 0, s, x, rows, dim, w, b, eps, y, q_inv_scale)
-  if (aligned && nv <= 4) TRIBE_RSN(4);
-  else if (aligned && nv <= 6) TRIBE_RSN(6);
-  else if (aligned && nv <= 8) TRIBE_RSN(8);
-  else if (aligned && nv <= 12) TRIBE_RSN(12);
-  else hipLaunchKernelGGL((rowstat_norm_kernel<OUT_BF16, LAYERNORM>), grid, dim3(256), 0, s, x, rows, dim, w, b, eps, y, q_inv_scale);
-#undef TRIBE_RSN
+  first_nv<4, 6, 8, 12, 0>([&](int nv) { return nv == 0 || (aligned && (dim / 4 + 63) / 64 <= nv); }, [&](auto nv) {
+    hipLaunchKernelGGL((rowstat_norm_kernel<OUT_BF16, LAYERNORM, decltype(nv)::value>), grid, dim3(256), 0, s, x, rows, dim, w, b, eps, y, q_inv_scale);
+  });
 }
 
 // Conv3d(stride == kernel) patch embedding as a GEMM: unfold pixels [B, F, C, H, W] into rows of
@@ -846,19 +732,13 @@ extern "C" int tribe_scalenorm_fwd(const float* x, int64_t rows, int64_t dim, co
   dim3 grid((unsigned)((rows + 3) / 4));
   hipStream_t s = (hipStream_t)stream;
   const bool aligned = ((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 8) == 0;
-#define TRIBE_SN_REG(NV)                                                                                                  \
-  do {                                                                                                                    \
-    if (y_dtype == TRIBE_BF16) hipLaunchKernelGGL((scalenorm_reg_kernel<1, NV>), grid, dim3(256), 0, s, x, rows, g, gain_scale, eps, y); \
-    else hipLaunchKernelGGL((scalenorm_reg_kernel<0, NV>), grid, dim3(256), 0, s, x, rows, g, gain_scale, eps, y);          \
-  } while (0)
-  if (aligned && dim == 3072) TRIBE_SN_REG(12);        // the TRIBE encoder width
-  else if (aligned && dim == 1024) TRIBE_SN_REG(4);
-  else if (aligned && dim == 768) TRIBE_SN_REG(3);     // the small test models
-  else if (y_dtype == TRIBE_BF16)
-    hipLaunchKernelGGL(scalenorm_kernel<1>, grid, dim3(256), 0, s, x, rows, dim, g, gain_scale, eps, y);
-  else
-    hipLaunchKernelGGL(scalenorm_kernel<0>, grid, dim3(256), 0, s, x, rows, dim, g, gain_scale, eps, y);
-#undef TRIBE_SN_REG
+  // NV: x 16-byte and y 8-byte aligned and dim = 3072 (the TRIBE encoder width) / 1024 / 768 (the small test models) -> the row in 12 / 4 / 3
+  // float4 per lane; else 0, the float4 walk (dim % 4 == 0: required above)
+  first_nv<12, 4, 3, 0>([&](int nv) { return nv == 0 || (aligned && dim == 256 * nv); }, [&](auto nv) {
+    constexpr int NV = decltype(nv)::value;
+    if (y_dtype == TRIBE_BF16) hipLaunchKernelGGL((scalenorm_kernel<1, NV>), grid, dim3(256), 0, s, x, rows, dim, g, gain_scale, eps, y);
+    else hipLaunchKernelGGL((scalenorm_kernel<0, NV>), grid, dim3(256), 0, s, x, rows, dim, g, gain_scale, eps, y);
+  });
   TRIBE_LAUNCH_CHECK();
   return 0;
 }
@@ -1048,11 +928,11 @@ int tribe_internal_softmax(const float* S, int64_t R, int64_t T, int64_t ld_s, u
                            hipStream_t stream) {
   const dim3 grid((unsigned)((R + 3) / 4));
   const bool reg = T_pad == T && T % 256 == 0 && T <= 2048 && ld_s % 4 == 0 && ld_p % 4 == 0 && ((uintptr_t)S % 16) == 0 && ((uintptr_t)P % 8) == 0;
-  if (reg && T == 256) hipLaunchKernelGGL(softmax_reg_kernel<1>, grid, dim3(256), 0, stream, S, R, ld_s, P, ld_p);
-  else if (reg && T == 512) hipLaunchKernelGGL(softmax_reg_kernel<2>, grid, dim3(256), 0, stream, S, R, ld_s, P, ld_p);
-  else if (reg && T == 1024) hipLaunchKernelGGL(softmax_reg_kernel<4>, grid, dim3(256), 0, stream, S, R, ld_s, P, ld_p);
-  else if (reg && T == 2048) hipLaunchKernelGGL(softmax_reg_kernel<8>, grid, dim3(256), 0, stream, S, R, ld_s, P, ld_p);
-  else hipLaunchKernelGGL(softmax_kernel, grid, dim3(256), 0, stream, S, R, T, ld_s, P, T_pad, ld_p);
+  // NV: T_pad == T, T = 256 / 512 / 1024 / 2048, the pitches multiples of 4, S 16-byte and P 8-byte aligned -> the row in 1 / 2 / 4 / 8 float4 per lane
+  if (!(reg && first_nv<1, 2, 4, 8>([&](int nv) { return T == 256 * nv; }, [&](auto nv) {
+          hipLaunchKernelGGL(softmax_reg_kernel<decltype(nv)::value>, grid, dim3(256), 0, stream, S, R, ld_s, P, ld_p);
+        })))
+    hipLaunchKernelGGL(softmax_kernel, grid, dim3(256), 0, stream, S, R, T, ld_s, P, T_pad, ld_p);
   TRIBE_LAUNCH_CHECK();
   return 0;
 }

@@ -5,9 +5,11 @@
 // One wave per row.  Row statistics and the two row means of the backward are f64 sums of the widened f32 values, rounded once; every
 // f32 step of the element arithmetic is an explicitly rounded operation (__fsub_rn / __fmul_rn / fmaf), so the register-resident, the
 // 16-byte-walk and the element kernels -- and the column-sum kernel that recomputes du and zh -- all form the same bits per element.
+// row_load / row_each, which give one kernel body its three forms, are in row_wave.h.
 #include <math.h>
 
 #include "common.h"
+#include "row_wave.h"
 
 namespace {
 
@@ -78,34 +80,6 @@ __device__ __forceinline__ void zero_pad(void* p, int bf16, int64_t dim, int64_t
   for (int64_t c = dim + lane; c < ld; c += 64) {
     if (bf16) ((unsigned short*)p)[c] = 0;
     else ((float*)p)[c] = 0.f;
-  }
-}
-
-// f(first column, values, register slot) over this lane's share of a row: NV > 0 -- the row as NV float4 per lane in `v` (columns
-// 4 * (lane + 64 j)); NV == 0 -- a walk over memory, 16 bytes (VEC) or one element at a time.  Without VEC only .x of the values counts.
-template <int NV, bool VEC, class F>
-__device__ __forceinline__ void row_each(const float* zr, const float4* v, int64_t dim, int lane, F f) {
-  if constexpr (NV > 0) {
-    const int n4 = (int)(dim >> 2);
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const int i = lane + 64 * j;
-      if (i < n4) f((int64_t)i * 4, v[j], j);
-    }
-  } else if constexpr (VEC) {
-    const int64_t n4 = dim >> 2;
-    for (int64_t i = lane; i < n4; i += 64) f(i * 4, *(const float4*)(zr + i * 4), 0);
-  } else {
-    for (int64_t c = lane; c < dim; c += 64) f(c, make_float4(zr[c], 0.f, 0.f, 0.f), 0);
-  }
-}
-template <int NV>
-__device__ __forceinline__ void row_load(const float* zr, float4* v, int64_t dim, int lane) {
-  const int n4 = (int)(dim >> 2);
-#pragma unroll
-  for (int j = 0; j < (NV > 0 ? NV : 1); ++j) {
-    const int i = lane + 64 * j;
-    v[j] = (NV > 0 && i < n4) ? *(const float4*)(zr + (int64_t)i * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
 }
 

@@ -34,7 +34,7 @@ Branches and the case that reaches each
     shapes                 (37, 200) with ld = 211 and K_pad = 256; K = 203 with K_pad = 208 (a group of four straddling K); (1, 16);
                            (2100, 1024): 2100 workgroups, ONE trip of the grid-stride loop.  The cap of 524 288 workgroups needs
                            more than 134 M groups of four (a 512 MiB output): left untested for its memory cost.
-  rowstat_norm(_reg)_kernel<2, .>   a NaN input row leaves as NaN codes, bit-identical to the two-pass form
+  rowstat_norm_kernel<2, ., NV>     a NaN input row leaves as NaN codes, bit-identical to the walk (NV = 0)
   absmax_kernel<float / bf16>
     (1, 1); (37, 200) with ld = 211 and a larger value parked in the skipped columns; (4100, 4096) f32: 4100 workgroups wanted,
     4096 launched, so the grid-stride loop makes a second trip.  The maximum is a NEGATIVE value in the first, a middle and the last

@@ -150,7 +150,7 @@ def _scores(R: int, T: int, seed: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
-# ScaleNorm forward: scalenorm_reg_kernel<OUT, 12 / 4 / 3> at 3072 / 1024 / 768, scalenorm_kernel at every other width
+# ScaleNorm forward: scalenorm_kernel<OUT, NV = 12 / 4 / 3> at 3072 / 1024 / 768, its walk (NV = 0) at every other width
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("out_dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("legacy", [False, True])
@@ -167,8 +167,8 @@ def test_scalenorm_fwd(ops, dim, legacy, out_dtype):
 
 
 # ------------------------------------------------------------------------------------------------
-# RMSNorm / LayerNorm forward: rowstat_norm_reg_kernel<OUT, LN, 4 / 6 / 8 / 12> for dim <= 1024 / 1536 / 2048 / 3072, else
-# rowstat_norm_kernel.  1028: NV 6 with the last slot filled by lane 0 alone; 3088, 4096: the generic walk
+# RMSNorm / LayerNorm forward: rowstat_norm_kernel<OUT, LN, NV = 4 / 6 / 8 / 12> for dim <= 1024 / 1536 / 2048 / 3072, else
+# its walk (NV = 0).  1028: NV 6 with the last slot filled by lane 0 alone; 3088, 4096: the generic walk
 # ------------------------------------------------------------------------------------------------
 ROWSTAT_DIMS = [16, 512, 1024, 1028, 1408, 2048, 3072, 3088, 4096]
 KINDS = ["rms", "ln", "ln_bias"]
