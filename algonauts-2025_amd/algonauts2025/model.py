@@ -38,6 +38,8 @@ norm, block and residual scaling; the draws use Python's `random` and are made o
 `causal` (extension, off by default) builds the encoder as x_transformers' Decoder: TR t attends to the stimulus up to t only.  The fused
 path gets it through the encoder's pack (tribe_encoder_fwd_ex), the training path hands it to autograd.RotaryAttention / Attention, which
 then take the materialised route with the causal row kernels at every attn_dropout; the dropouts above compose with it unchanged.
+A causal model can be followed step by step: `stream(batch_size, max_len)` returns an `EncoderStream` whose `push(one stimulus step)` runs
+the projectors with row `pos` of time_pos_embed, HipEncoder.step on a KV cache and the voxel head at one time step (eval semantics only).
 """
 
 from __future__ import annotations
@@ -205,8 +207,11 @@ class FmriEncoder(nn.Module):
             drop = list(np.random.choice(drop, len(drop) - 1, replace=False))
         return drop
 
-    def _fused_embed(self, data: dict[str, torch.Tensor], add_embeddings: bool) -> tuple[torch.Tensor, int, int]:
-        """aggregate_features (+ transformer_forward's embedding adds when `add_embeddings`): f32 [B*T, hidden]."""
+    def _fused_embed(self, data: dict[str, torch.Tensor], add_embeddings: bool, pos0: int = 0, draw: bool = True
+                     ) -> tuple[torch.Tensor, int, int]:
+        """aggregate_features (+ transformer_forward's embedding adds when `add_embeddings`): f32 [B*T, hidden].
+        pos0: the position of the first time step (a stream's steps: rows pos0 .. pos0 + T - 1 of time_pos_embed); draw=False: no
+        modality-dropout draw (streaming is eval-only and leaves the RNG alone)."""
         for modality in data.keys():
             if modality in self.feature_dims:
                 break
@@ -219,10 +224,10 @@ class FmriEncoder(nn.Module):
             # reference behaviour: a 3072//n zero block cannot be summed with hidden-wide projections (model.py:143-144,163-164)
             raise RuntimeError(f"The size of tensor a ({self.hidden}) must match the size of tensor b ({self.hidden // n_mod}) "
                                "at non-singleton dimension 2")
-        if add_embeddings and T > self.time_pos_embed.shape[1]:
-            raise RuntimeError(f"sequence length {T} exceeds the positional table ({self.time_pos_embed.shape[1]})")
-        dropped = self._draw_modality_dropout()
-        pos = f32c(self.time_pos_embed)[0] if add_embeddings else None
+        if add_embeddings and pos0 + T > self.time_pos_embed.shape[1]:
+            raise RuntimeError(f"sequence length {pos0 + T} exceeds the positional table ({self.time_pos_embed.shape[1]})")
+        dropped = self._draw_modality_dropout() if draw else []
+        pos = f32c(self.time_pos_embed)[0][pos0:] if add_embeddings else None
         semb, sid = None, None
         if add_embeddings and hasattr(self, "subject_embed"):
             semb = f32c(self.subject_embed.weight)
@@ -407,6 +412,15 @@ class FmriEncoder(nn.Module):
             out = ops.adaptive_avg_pool(out, self.n_output_timesteps)
         return out
 
+    # --- streaming (causal encoders): one stimulus step at a time ------------------------------------
+    def stream(self, batch_size: int, max_len: int | None = None) -> "EncoderStream":
+        """A stream of `batch_size` timelines of up to `max_len` stimulus steps (None: config.max_timesteps) through this model:
+        EncoderStream.push(one step) -> the prediction at that step.  Needs `causal=True`."""
+        max_len = self.config.max_timesteps if max_len is None else max_len
+        if max_len > self.time_pos_embed.shape[1]:
+            raise ValueError(f"FmriEncoder.stream: max_len={max_len} exceeds the positional table ({self.time_pos_embed.shape[1]} steps)")
+        return EncoderStream(self, batch_size, max_len)
+
     # --- contrastive alignment helpers (model.py:177-241) -----------------------------------------
     @torch.no_grad()
     def get_brain_latents(self, batch: SegmentData | dict) -> torch.Tensor:
@@ -479,3 +493,74 @@ class FmriEncoder(nn.Module):
                 lat = ops.adaptive_avg_pool(lat.transpose(1, 2).contiguous(), brain.size(1)).transpose(1, 2)
             losses[modality] = self._info_nce(brain, lat, tau=self.config.contrastive_temperature)
         return losses
+
+
+class EncoderStream:
+    """A causal FmriEncoder followed step by step (FmriEncoder.stream): the encoder's keys and values of the steps seen so far live in an
+    EncoderCache, so a new 0.5 s stimulus step costs one row per GEMM and a matrix-vector attention instead of a forward over the window.
+
+    Outputs are on the un-pooled stimulus grid (`forward(batch, pool_outputs=False)`'s columns): adaptive pooling to TRs needs the whole
+    window and stays with the caller.  Inference only: eval semantics whatever `model.training` says -- no modality dropout, none of the
+    encoder's or projectors' dropouts, no autograd graph.  The voxel head runs its usual form (rows = voxels of the sample's subject,
+    N = T = 1 column)."""
+
+    def __init__(self, model: FmriEncoder, batch_size: int, max_len: int):
+        self.model = model
+        self.cache = model.encoder.new_cache(batch_size, max_len, model.time_pos_embed.device)
+
+    @property
+    def pos(self) -> int:
+        return self.cache.pos
+
+    def reset(self) -> None:
+        self.cache.reset()
+
+    def _steps(self, what: str, data: dict[str, torch.Tensor], one: bool) -> int:
+        """Validates a push / prefill batch before anything is launched; returns its number of time steps."""
+        T = None
+        for modality in self.model.feature_dims:
+            feat = data.get(modality) if modality in self.model.projectors else None
+            if feat is None:
+                continue
+            if feat.ndim not in (3, 4):
+                raise ValueError(f"EncoderStream.{what}: {modality}: expected [B, L, D, T] or [B, D, T] features, got {tuple(feat.shape)}")
+            if feat.shape[0] != self.cache.batch_size:
+                raise ValueError(f"EncoderStream.{what}: {modality}: batch size {feat.shape[0]} does not match the stream's {self.cache.batch_size}")
+            if feat.device != self.cache.device:
+                raise ValueError(f"EncoderStream.{what}: {modality} is on {feat.device}, the stream on {self.cache.device}")
+            if T is not None and feat.shape[-1] != T:
+                raise ValueError(f"EncoderStream.{what}: modalities disagree on the number of time steps ({T} vs {feat.shape[-1]})")
+            T = feat.shape[-1]
+        if T is None:
+            raise ValueError(f"EncoderStream.{what}: the batch holds none of the modalities {list(self.model.projectors)}")
+        if one and T != 1:
+            raise ValueError(f"EncoderStream.{what}: expected one time step per call ([B, L, D, 1] or [B, D, 1]), got {T}")
+        if self.cache.pos + T > self.cache.max_len:
+            raise ValueError(f"EncoderStream.{what}: {self.cache.pos} steps seen + {T} would run past max_len={self.cache.max_len}")
+        return T
+
+    @torch.no_grad()
+    def push(self, data: SegmentData | dict) -> torch.Tensor:
+        """One stimulus step of every timeline: each modality [B, L, D, 1] or [B, D, 1], plus `subject_id` -> f32 [B, n_outputs], the
+        prediction at this step given the steps pushed so far."""
+        model = self.model
+        data = model._batch_dict(data)
+        self._steps("push", data, one=True)
+        x, B, _ = model._fused_embed(data, add_embeddings=True, pos0=self.cache.pos, draw=False)
+        model.encoder._check_stream("step", x, self.cache, 1)
+        y = model.encoder.step_tokens(x, self.cache, torch.bfloat16)
+        return model.predictor.forward_tokens(y.view(B, 1, -1), data["subject_id"])[:, :, 0]
+
+    @torch.no_grad()
+    def prefill(self, data: SegmentData | dict) -> torch.Tensor:
+        """The first T0 steps at once, into an empty stream: each modality [B, L, D, T0] or [B, D, T0] -> f32 [B, n_outputs, T0]; `push`
+        continues at step T0."""
+        model = self.model
+        data = model._batch_dict(data)
+        if self.cache.pos != 0:
+            raise ValueError(f"EncoderStream.prefill: the stream already holds {self.cache.pos} steps; prefill starts from an empty one (reset())")
+        T = self._steps("prefill", data, one=False)
+        x, B, _ = model._fused_embed(data, add_embeddings=True, draw=False)
+        model.encoder._check_stream("prefill", x.view(B, T, -1), self.cache, T)
+        y = model.encoder.prefill_tokens(x, B, T, self.cache, torch.bfloat16)
+        return model.predictor.forward_tokens(y.view(B, T, -1), data["subject_id"])

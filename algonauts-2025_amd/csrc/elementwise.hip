@@ -5,6 +5,7 @@
 // The norms (scalenorm_kernel<OUT, NV>, rowstat_norm_kernel<OUT, LN, NV>) are one template each over row_wave.h:
 // NV > 0 keeps the row in registers, NV == 0 walks it once per pass.
 #include "common.h"
+#include "rotary_pairs.h"
 #include "row_wave.h"
 #include "softmax_row.h"
 
@@ -164,21 +165,11 @@ __global__ __launch_bounds__(256) void rotary_kernel(unsigned short* __restrict_
     const float cs[4] = {c.x, c.y, c.z, c.w}, sn[4] = {s.x, s.y, s.z, s.w};
     if (interleaved) {
       u16x8_t v = *(u16x8_t*)(base + it * 8);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const float a = bf16_to_f32(v[2 * p]), b = bf16_to_f32(v[2 * p + 1]);
-        v[2 * p] = f32_to_bf16(a * cs[p] - b * sn[p]);
-        v[2 * p + 1] = f32_to_bf16(b * cs[p] + a * sn[p]);
-      }
+      rotate_interleaved8(v, cs, sn);
       *(u16x8_t*)(base + it * 8) = v;
     } else {
       u16x4_t lo = *(u16x4_t*)(base + it * 4), hi = *(u16x4_t*)(base + half + it * 4);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const float a = bf16_to_f32(lo[p]), b = bf16_to_f32(hi[p]);
-        lo[p] = f32_to_bf16(a * cs[p] - b * sn[p]);
-        hi[p] = f32_to_bf16(b * cs[p] + a * sn[p]);
-      }
+      rotate_split4(lo, hi, cs, sn);
       *(u16x4_t*)(base + it * 4) = lo;
       *(u16x4_t*)(base + half + it * 4) = hi;
     }

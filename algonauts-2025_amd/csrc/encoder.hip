@@ -11,6 +11,9 @@ int tribe_internal_attention_fused_supported(int dim_head);
 int tribe_internal_attention_fused(const uint16_t* qkv, int64_t B, int64_t T, int heads, int dim_head, float scale, uint16_t* out,
                                    hipStream_t s);
 
+int tribe_internal_kv_fill(const uint16_t* qkv, int64_t B, int64_t T, int heads, int dim_head, uint16_t* k_cache, uint16_t* v_cache,
+                           int64_t cap, hipStream_t stream);
+
 void tribe_internal_attention_set_wide384(int on);
 void tribe_internal_attention_set_d64_variant(int v);
 int tribe_internal_attention_rotates_q(int dim_head);
@@ -169,6 +172,19 @@ inline EncLayout layout(const tribe_encoder_desc* d, Arena& ws) {
   p.split_ws = p.split_bytes ? ws.take<void>(p.split_bytes) : nullptr;
   return p;
 }
+// where a prefill leaves every layer's rotated k heads and v heads: caches [depth, B, heads, cap, dim_head]
+struct KvSink {
+  uint16_t *k, *v;
+  int64_t cap;
+};
+// A GEMM of a small batch may run split over K: hand it the workspace when the launcher says it would use one
+inline void allow_split_k(tribe_gemm_desc& g, void* split_ws, size_t split_bytes) {
+  if (split_bytes == 0) return;
+  g.stream_k = 1;
+  const int64_t need = tribe_gemm_stream_k_workspace_bytes(&g);
+  if (need > 0 && (size_t)need <= split_bytes) { g.stream_k_ws = split_ws; g.stream_k_ws_bytes = (int64_t)split_bytes; }
+  else g.stream_k = 0;
+}
 inline int enc_validate(const tribe_encoder_desc* d) {
   TRIBE_REQUIRE(d != nullptr, "tribe_encoder: null descriptor");
   TRIBE_REQUIRE(d->B > 0 && d->T > 0 && d->dim > 0 && d->depth >= 0 && d->heads > 0 && d->dim_head > 0 && d->ff_inner > 0,
@@ -189,9 +205,10 @@ extern "C" size_t tribe_encoder_workspace_bytes(const tribe_encoder_desc* d) {
   return ws.off;
 }
 
-// the body of tribe_encoder_fwd (flags = 0) and tribe_encoder_fwd_ex
+// the body of tribe_encoder_fwd (flags = 0), tribe_encoder_fwd_ex and tribe_encoder_prefill_fwd (causal, with a sink: one more launch
+// per layer, after the rotary pass; without a sink the launches are what they were)
 static int encoder_fwd_body(const tribe_encoder_desc* d, uint32_t flags, float* x, void* y, int32_t y_dtype, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+                            size_t workspace_bytes, void* stream, const KvSink* sink = nullptr) {
   int rc = enc_validate(d);
   if (rc) return rc;
   const bool causal = (flags & TRIBE_ENCODER_CAUSAL) != 0;
@@ -203,14 +220,7 @@ static int encoder_fwd_body(const tribe_encoder_desc* d, uint32_t flags, float* 
   const int64_t M = p.M, inner = p.inner, dim = d->dim;
   uint16_t *xn = p.xn, *qkv = p.qkv, *ao = p.ao, *hbuf = p.hbuf;
   float *ssq = p.ssq, *rowf = p.rowf;
-  // a GEMM of a small batch may run split over K: hand it the workspace when the launcher says it would use one
-  auto allow_split = [&](tribe_gemm_desc& g) {
-    if (p.split_bytes == 0) return;
-    g.stream_k = 1;
-    const int64_t need = tribe_gemm_stream_k_workspace_bytes(&g);
-    if (need > 0 && (size_t)need <= p.split_bytes) { g.stream_k_ws = p.split_ws; g.stream_k_ws_bytes = (int64_t)p.split_bytes; }
-    else g.stream_k = 0;
-  };
+  auto allow_split = [&](tribe_gemm_desc& g) { allow_split_k(g, p.split_ws, p.split_bytes); };
   int64_t n_part = dim / 64;   // slots per row the LAST producer wrote (one per wave column group of its tile: tribe_gemm_sumsq_slots)
   const float scale = 1.0f / sqrtf((float)d->dim_head);
   // With whole 256-column tiles the pre-norms are folded into the GEMMs: the GEMM that writes x also leaves bf16(x) in `xn` and
@@ -270,6 +280,12 @@ static int encoder_fwd_body(const tribe_encoder_desc* d, uint32_t flags, float* 
                                         d->rotary_interleaved, stream);
       if (rc) return rc;
     }
+    if (sink) {   // the rotated k heads and the v heads of all T positions into slots 0 .. T-1 of this layer's caches
+      const int64_t per_layer = d->B * inner * sink->cap;
+      rc = tribe_internal_kv_fill(qkv, d->B, d->T, d->heads, d->dim_head, sink->k + l * per_layer, sink->v + l * per_layer, sink->cap,
+                                  (hipStream_t)stream);
+      if (rc) return rc;
+    }
     if (causal) {   // the fused kernel under the mask (the 16-row kernel at every head size): q and k arrive rotated
       tribe_attention_desc a{};
       a.q = qkv; a.k = qkv + inner; a.v = qkv + 2 * inner;
@@ -327,6 +343,103 @@ extern "C" int tribe_encoder_fwd_ex(const tribe_encoder_desc* d, uint32_t flags,
   TRIBE_REQUIRE((flags & ~TRIBE_ENCODER_CAUSAL) == 0, "tribe_encoder_fwd_ex: unknown flag bits 0x%x (known: TRIBE_ENCODER_CAUSAL = 1)",
                 (unsigned)(flags & ~TRIBE_ENCODER_CAUSAL));
   return encoder_fwd_body(d, flags, x, y, y_dtype, workspace, workspace_bytes, stream);
+}
+
+// ---- streaming: a causal encoder one position at a time (attn_decode.hip) ----
+extern "C" int tribe_encoder_prefill_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache,
+                                         uint16_t* v_cache, int64_t cap, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_prefill_fwd: null descriptor");
+  TRIBE_REQUIRE(x && y && workspace && k_cache && v_cache, "tribe_encoder_prefill_fwd: null pointer");
+  TRIBE_REQUIRE(d->T > 0 && d->T <= cap, "tribe_encoder_prefill_fwd: T=%lld positions do not fit the cache capacity %lld", (long long)d->T,
+                (long long)cap);
+  TRIBE_REQUIRE(((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0, "tribe_encoder_prefill_fwd: caches must be 16-byte aligned");
+  const KvSink sink{k_cache, v_cache, cap};
+  return encoder_fwd_body(d, TRIBE_ENCODER_CAUSAL, x, y, y_dtype, workspace, workspace_bytes, stream, &sink);
+}
+
+namespace {
+struct StepLayout {
+  int64_t inner;
+  uint16_t* xn;     // [B, dim] bf16 input of QKV / FF1
+  uint16_t* qkv;    // [B, 3*inner]
+  uint16_t* ao;     // [B, inner], behind qkv
+  uint16_t* hbuf;   // [B, ff_inner], over qkv | ao (dead by then)
+  void* attn_ws; size_t attn_bytes;
+  void* split_ws; size_t split_bytes;
+};
+inline StepLayout step_layout(const tribe_encoder_desc* d, int64_t cap, Arena& ws) {
+  StepLayout p;
+  const int64_t M = d->B, inner = p.inner = (int64_t)d->heads * d->dim_head;
+  p.xn = ws.take<uint16_t>((size_t)M * d->dim * 2);
+  const int64_t wide = (4 * inner > d->ff_inner) ? 4 * inner : d->ff_inner;
+  p.qkv = p.hbuf = ws.take<uint16_t>((size_t)M * wide * 2);
+  p.ao = p.qkv + (size_t)M * 3 * inner;
+  p.attn_bytes = tribe_attention_decode_workspace_bytes(d->B, d->heads, d->dim_head, cap);   // the most parts any n <= cap has
+  p.attn_ws = ws.take<void>(p.attn_bytes);
+  const int64_t widest = 3 * inner > d->ff_inner ? (3 * inner > d->dim ? 3 * inner : d->dim) : (d->ff_inner > d->dim ? d->ff_inner : d->dim);
+  p.split_bytes = align256((size_t)8 * M * widest * 4);   // every GEMM of a step is far under one round of tiles (encoder_fwd_body's allowance)
+  p.split_ws = ws.take<void>(p.split_bytes);
+  return p;
+}
+}  // namespace
+
+extern "C" size_t tribe_encoder_step_workspace_bytes(const tribe_encoder_desc* d, int64_t cap) {
+  if (!d || d->B <= 0 || cap <= 0) return 0;
+  Arena ws;
+  step_layout(d, cap, ws);
+  return ws.off;
+}
+
+extern "C" int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+                                      int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_step_fwd: null descriptor");
+  int rc = enc_validate(d);
+  if (rc) return rc;
+  TRIBE_REQUIRE(x && y && workspace && k_cache && v_cache, "tribe_encoder_step_fwd: null pointer");
+  TRIBE_REQUIRE(d->T == 1, "tribe_encoder_step_fwd: a step is one position per sequence (T=%lld)", (long long)d->T);
+  TRIBE_REQUIRE(cap > 0 && pos >= 0 && pos < cap, "tribe_encoder_step_fwd: pos=%lld outside the cache capacity %lld", (long long)pos, (long long)cap);
+  TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "tribe_encoder_step_fwd: workspace must be 256-byte aligned");
+  Arena ws(workspace);
+  const StepLayout p = step_layout(d, cap, ws);
+  TRIBE_REQUIRE(workspace_bytes >= ws.off, "tribe_encoder_step_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+  const int64_t M = d->B, inner = p.inner, dim = d->dim;
+  const int64_t per_layer = d->B * inner * cap;
+  const float scale = 1.0f / sqrtf((float)d->dim_head);
+  // M = B rows never fill the 256-column tiles of rows the fused-norm GEMM path needs: every ScaleNorm is its own launch
+  for (int l = 0; l < d->depth; ++l) {
+    const tribe_encoder_layer& L = d->layers_host[l];
+    TRIBE_REQUIRE(L.attn_norm_g && L.w_qkv && L.w_out && L.ff_norm_g && L.w_ff1 && L.b_ff1 && L.w_ff2 && L.b_ff2,
+                  "tribe_encoder_step_fwd: layer %d has a null parameter", l);
+    rc = tribe_scalenorm_fwd(x, M, dim, L.attn_norm_g, d->norm_gain_scale, d->norm_eps, p.xn, TRIBE_BF16, stream);
+    if (rc) return rc;
+    tribe_gemm_desc g = Linear(TRIBE_ROLE_QKV, M, p.xn, dim, L.w_qkv, nullptr, p.qkv, 3 * inner, TRIBE_BF16);
+    allow_split_k(g, p.split_ws, p.split_bytes);
+    rc = tribe_gemm_bf16(&g, stream);
+    if (rc) return rc;
+    uint16_t *kc = k_cache + l * per_layer, *vc = v_cache + l * per_layer;
+    rc = tribe_kv_append(p.qkv, d->B, d->heads, d->dim_head, d->rot_dim, d->rotary_interleaved, d->cos_tab, d->sin_tab, pos, kc, vc, cap, stream);
+    if (rc) return rc;
+    rc = tribe_attention_decode_fwd(p.qkv, 3 * inner, kc, vc, d->B, d->heads, d->dim_head, cap, pos + 1, scale, p.ao, p.attn_ws, p.attn_bytes,
+                                    stream);
+    if (rc) return rc;
+    g = Linear(TRIBE_ROLE_OUT_PROJ, M, p.ao, inner, L.w_out, nullptr, x, dim, TRIBE_F32).residual(x);
+    g.res_scale = L.attn_res_scale;
+    allow_split_k(g, p.split_ws, p.split_bytes);
+    rc = tribe_gemm_bf16(&g, stream);
+    if (rc) return rc;
+    rc = tribe_scalenorm_fwd(x, M, dim, L.ff_norm_g, d->norm_gain_scale, d->norm_eps, p.xn, TRIBE_BF16, stream);
+    if (rc) return rc;
+    g = Linear(TRIBE_ROLE_FF1, M, p.xn, dim, L.w_ff1, L.b_ff1, p.hbuf, d->ff_inner, TRIBE_BF16).activation(TRIBE_ACT_GELU);
+    allow_split_k(g, p.split_ws, p.split_bytes);
+    rc = tribe_gemm_bf16(&g, stream);
+    if (rc) return rc;
+    g = Linear(TRIBE_ROLE_FF2, M, p.hbuf, d->ff_inner, L.w_ff2, L.b_ff2, x, dim, TRIBE_F32).residual(x);
+    g.res_scale = L.ff_res_scale;
+    allow_split_k(g, p.split_ws, p.split_bytes);
+    rc = tribe_gemm_bf16(&g, stream);
+    if (rc) return rc;
+  }
+  return tribe_scalenorm_fwd(x, M, dim, d->final_norm_g, d->norm_gain_scale, d->norm_eps, y, y_dtype, stream);
 }
 
 extern "C" int tribe_voxel_head_fwd(const uint16_t* x, int64_t B, int64_t T, int64_t C_pad, const uint16_t* w_packed, int64_t S,

@@ -25,6 +25,12 @@ fused inference path runs tribe_encoder_fwd_ex with TRIBE_ENCODER_CAUSAL (q and 
 flash kernel).  The training path (FmriEncoder) passes it to modeling_utils.autograd.Attention / RotaryAttention, which then take the
 materialised route at every attn_dropout, 0 included, with the causal softmax row kernels (csrc/attn_softmax.hip); the three dropout fields
 compose with it unchanged.  dim_head must be one the flash kernel is built for (64, 128, 192, 384).
+
+A causal encoder can also be followed one position at a time: `new_cache(batch_size, max_len)` makes an `EncoderCache` (every layer's
+rotated keys and values, bf16 [depth, B, heads, max_len, dim_head]), `step(x[B, dim], cache)` gives the output at position `cache.pos` from
+one row per GEMM and a single-query attention against the cache (tribe_encoder_step_fwd: tribe_kv_append + tribe_attention_decode_fwd per
+layer, csrc/attn_decode.hip), and `prefill(x[B, T0, dim], cache)` is the causal forward over the first T0 positions that also fills the
+cache (tribe_encoder_prefill_fwd).  Inference only, like `forward`.
 """
 
 from __future__ import annotations
@@ -85,6 +91,34 @@ class _Rotary(nn.Module):
     def __init__(self, dim: int, base: float = 10000.0):
         super().__init__()
         self.register_buffer("inv_freq", 1.0 / (base ** (torch.arange(0, dim, 2).float() / dim)))
+
+
+class EncoderCache:
+    """The keys and values of a streamed causal encoder (HipEncoder.new_cache): `k`, `v` bf16 [depth, B, heads, max_len, dim_head] -- the
+    rotated k heads and the v heads of every position seen so far, each (layer, sequence, head) one contiguous run -- and `pos`, the
+    number of positions filled.  2 * depth * B * heads * max_len * dim_head * 2 bytes."""
+
+    def __init__(self, depth: int, batch_size: int, heads: int, max_len: int, dim_head: int, device: torch.device | str | None):
+        shape = (depth, batch_size, heads, max_len, dim_head)
+        self.k = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        self.v = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        self.pos = 0
+
+    @property
+    def batch_size(self) -> int:
+        return self.k.shape[1]
+
+    @property
+    def max_len(self) -> int:
+        return self.k.shape[3]
+
+    @property
+    def device(self) -> torch.device:
+        return self.k.device
+
+    def reset(self) -> None:
+        """Forget every position: the next step is position 0 again.  (The slots are not cleared: nothing at or beyond `pos` is read.)"""
+        self.pos = 0
 
 
 class HipEncoder(nn.Module):
@@ -177,6 +211,74 @@ class HipEncoder(nn.Module):
             raise ValueError(f"HipEncoder: expected last dim {self.dim}, got {D}")
         x2d = x.detach().to(torch.float32).reshape(B * T, D).clone()
         return self.forward_tokens(x2d, B, T, torch.float32).view(B, T, D)
+
+    # -- streaming: one position at a time (causal encoders only) ----------------------------
+    def new_cache(self, batch_size: int, max_len: int, device: torch.device | str | None = None) -> EncoderCache:
+        """An empty cache for `batch_size` sequences of up to `max_len` positions, on `device` (default: where the parameters are)."""
+        self._require_causal("new_cache")
+        if batch_size < 1 or max_len < 1:
+            raise ValueError(f"HipEncoder.new_cache: batch_size={batch_size} and max_len={max_len} must be positive")
+        if device is None:
+            device = next(self.parameters()).device
+        return EncoderCache(self.depth, batch_size, self.heads, max_len, self.dim_head, device)
+
+    def _require_causal(self, what: str) -> None:
+        if not self.causal:
+            raise ValueError(f"HipEncoder.{what}: a bidirectional encoder (causal=False) has no incremental form: every output depends on "
+                             "the whole window")
+
+    def _check_stream(self, what: str, x: torch.Tensor, cache: EncoderCache, steps: int) -> None:
+        self._require_causal(what)
+        if not isinstance(cache, EncoderCache):
+            raise TypeError(f"HipEncoder.{what}: cache must be an EncoderCache (HipEncoder.new_cache), got {type(cache)}")
+        want = (self.depth, cache.batch_size, self.heads, cache.max_len, self.dim_head)
+        if tuple(cache.k.shape) != want:
+            raise ValueError(f"HipEncoder.{what}: the cache {tuple(cache.k.shape)} was not made for this encoder ({want})")
+        if x.shape[0] != cache.batch_size:
+            raise ValueError(f"HipEncoder.{what}: batch size {x.shape[0]} does not match the cache's {cache.batch_size}")
+        if x.shape[-1] != self.dim:
+            raise ValueError(f"HipEncoder.{what}: expected last dim {self.dim}, got {x.shape[-1]}")
+        if x.device != cache.device:
+            raise ValueError(f"HipEncoder.{what}: x is on {x.device}, the cache on {cache.device}")
+        if cache.pos + steps > cache.max_len:
+            raise ValueError(f"HipEncoder.{what}: {cache.pos} positions filled + {steps} would run past max_len={cache.max_len}")
+
+    def prefill_tokens(self, x2d: torch.Tensor, B: int, T: int, cache: EncoderCache, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+        """x2d f32 [B*T, dim], CONSUMED -> y [B*T, dim]; fills the empty cache with positions 0 .. T-1."""
+        y = ops.encoder_prefill(x2d, self.packed(), cache.k, cache.v, T, out_dtype)
+        cache.pos = T
+        return y
+
+    def step_tokens(self, x2d: torch.Tensor, cache: EncoderCache, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+        """x2d f32 [B, dim], CONSUMED -> y [B, dim] at position cache.pos, which advances."""
+        y = ops.encoder_step(x2d, self.packed(), cache.k, cache.v, cache.pos, out_dtype)
+        cache.pos += 1
+        return y
+
+    def prefill(self, x: torch.Tensor, cache: EncoderCache) -> torch.Tensor:
+        """x [B, T0, dim] -> y [B, T0, dim]: the causal forward over the first T0 positions, which leaves their keys and values in the
+        (empty) cache so that `step` continues at position T0.  Inference only, like `forward` / `forward_tokens`: eval semantics, none of
+        attn_dropout, ff_dropout, layer_dropout."""
+        if x.ndim != 3:
+            raise ValueError(f"HipEncoder.prefill: expected [B, T0, dim], got {tuple(x.shape)}")
+        B, T0, D = x.shape
+        self._check_stream("prefill", x, cache, T0)
+        if cache.pos != 0:
+            raise ValueError(f"HipEncoder.prefill: the cache already holds {cache.pos} positions; prefill starts from an empty cache (cache.reset())")
+        if T0 < 1:
+            raise ValueError("HipEncoder.prefill: T0 must be at least 1")
+        x2d = x.detach().to(torch.float32).reshape(B * T0, D).clone()
+        return self.prefill_tokens(x2d, B, T0, cache, torch.float32).view(B, T0, D)
+
+    def step(self, x: torch.Tensor, cache: EncoderCache) -> torch.Tensor:
+        """x [B, dim], the encoder input at position cache.pos -> y [B, dim], the output there: equal (to rounding) to row cache.pos of
+        `forward` on the whole sequence so far, at the cost of one row per GEMM and a matrix-vector attention against the cache.  Advances
+        cache.pos.  Inference only, like `forward` / `forward_tokens`: eval semantics, none of attn_dropout, ff_dropout, layer_dropout."""
+        if x.ndim != 2:
+            raise ValueError(f"HipEncoder.step: expected [B, dim], got {tuple(x.shape)}")
+        self._check_stream("step", x, cache, 1)
+        x2d = x.detach().to(torch.float32).clone().contiguous()
+        return self.step_tokens(x2d, cache, torch.float32)
 
 
 class TransformerEncoderConfig(pydantic.BaseModel):

@@ -732,12 +732,7 @@ class EncoderPack:
         return self._tabs[key]
 
 
-def encoder_fwd(x: torch.Tensor, pack: EncoderPack, B: int, T: int, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
-    """x f32 [B*T, dim] is consumed (updated in place); returns final-normed y [B*T, dim]."""
-    _cuda(x, torch.float32, "x")
-    if x.shape != (B * T, pack.dim):
-        raise ValueError(f"encoder_fwd: x must be [{B * T}, {pack.dim}], got {tuple(x.shape)}")
-    cos, sin = pack.tables(T, x.device)
+def _encoder_desc(pack: EncoderPack, B: int, T: int, cos: torch.Tensor | None, sin: torch.Tensor | None) -> EncoderDesc:
     d = EncoderDesc()
     d.B, d.T = B, T
     d.dim, d.depth, d.heads, d.dim_head, d.ff_inner = pack.dim, pack.depth, pack.heads, pack.dim_head, pack.ff_inner
@@ -746,6 +741,15 @@ def encoder_fwd(x: torch.Tensor, pack: EncoderPack, B: int, T: int, out_dtype: t
     d.layers_host = C.cast(pack.layers, C.POINTER(EncoderLayer))
     d.final_norm_g = pack.final_norm_g.data_ptr()
     d.cos_tab, d.sin_tab = _p(cos), _p(sin)
+    return d
+
+
+def encoder_fwd(x: torch.Tensor, pack: EncoderPack, B: int, T: int, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """x f32 [B*T, dim] is consumed (updated in place); returns final-normed y [B*T, dim]."""
+    _cuda(x, torch.float32, "x")
+    if x.shape != (B * T, pack.dim):
+        raise ValueError(f"encoder_fwd: x must be [{B * T}, {pack.dim}], got {tuple(x.shape)}")
+    d = _encoder_desc(pack, B, T, *pack.tables(T, x.device))
     y = torch.empty(B * T, pack.dim, dtype=out_dtype, device=x.device)
     nbytes = lib().tribe_encoder_workspace_bytes(C.byref(d))
     ws = workspace(nbytes, x.device)
@@ -755,6 +759,140 @@ def encoder_fwd(x: torch.Tensor, pack: EncoderPack, B: int, T: int, out_dtype: t
         return y
     check(lib().tribe_encoder_fwd(C.byref(d), x.data_ptr(), y.data_ptr(), _DT[out_dtype], ws.data_ptr(), ws.numel(), _stream()),
           "tribe_encoder_fwd")
+    return y
+
+
+# --------------------------------------------------------------------------------------
+# streaming a causal encoder: KV cache, single-query attention, one-position encoder step
+# --------------------------------------------------------------------------------------
+DECODE_DIM_HEADS = (64, 128, 192, 384)
+
+
+def _kv_caches(what: str, k_cache: torch.Tensor, v_cache: torch.Tensor, ndim: int) -> tuple[int, ...]:
+    """Shape of a K / V cache pair ([B, heads, cap, dim_head], or with a leading depth), checked before any device work."""
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t)}")
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"{what}: {name} must be bfloat16, got {t.dtype}")
+        if t.ndim != ndim or not t.is_contiguous():
+            lead = "depth, " if ndim == 5 else ""
+            raise ValueError(f"{what}: {name} must be a contiguous [{lead}B, heads, cap, dim_head] tensor, got shape {tuple(t.shape)}")
+    if k_cache.shape != v_cache.shape or k_cache.device != v_cache.device:
+        raise ValueError(f"{what}: k_cache {tuple(k_cache.shape)} on {k_cache.device} and v_cache {tuple(v_cache.shape)} on {v_cache.device} differ")
+    return tuple(k_cache.shape)
+
+
+def _step_rows(what: str, t: torch.Tensor, name: str, dtype: torch.dtype, B: int, min_width: int, device: torch.device) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t)}")
+    if t.dtype != dtype:
+        raise TypeError(f"{what}: {name} must be {dtype}, got {t.dtype}")
+    if t.ndim != 2 or t.shape[0] != B or t.shape[1] < min_width or t.stride(1) != 1:
+        raise ValueError(f"{what}: {name} must be [B={B}, >= {min_width}] with unit column stride, got shape {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{what}: {name} is on {t.device}, the caches on {device}")
+
+
+def kv_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: int, rot_dim: int, cos: torch.Tensor | None,
+              sin: torch.Tensor | None, interleaved: bool) -> torch.Tensor:
+    """tribe_kv_append: rotates the q and k heads of the step's fused bf16 qkv [B, 3*heads*dim_head] in place at position `pos`
+    (ops.rotary_'s bits; cos / sin f32 [> pos, rot_dim/2], unused at rot_dim == 0) and stores the rotated k heads and the v heads into slot
+    `pos` of the bf16 caches [B, heads, cap, dim_head].  Returns qkv."""
+    what = "tribe_kv_append"
+    B, heads, cap, dim_head = _kv_caches(what, k_cache, v_cache, 4)
+    _step_rows(what, qkv, "qkv", torch.bfloat16, B, 3 * heads * dim_head, k_cache.device)
+    if qkv.shape[1] != 3 * heads * dim_head or not qkv.is_contiguous():
+        raise ValueError(f"{what}: qkv must be contiguous [B={B}, 3*heads*dim_head={3 * heads * dim_head}], got shape {tuple(qkv.shape)}")
+    if not 0 <= pos < cap:
+        raise ValueError(f"{what}: pos={pos} outside the cache capacity {cap}")
+    if rot_dim:
+        for name, t in (("cos", cos), ("sin", sin)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 2 or t.shape[1] != rot_dim // 2 or t.shape[0] <= pos \
+                    or not t.is_contiguous() or t.device != k_cache.device:
+                raise ValueError(f"{what}: {name} must be a contiguous f32 [> pos={pos}, rot_dim/2={rot_dim // 2}] table on {k_cache.device}")
+    _cuda(qkv, torch.bfloat16, "qkv")
+    check(lib().tribe_kv_append(qkv.data_ptr(), B, heads, dim_head, rot_dim, int(interleaved), _p(cos) if rot_dim else None,
+                                _p(sin) if rot_dim else None, pos, k_cache.data_ptr(), v_cache.data_ptr(), cap, _stream()), what)
+    return qkv
+
+
+def attention_decode_splits(B: int, heads: int, n: int) -> int:
+    """Workgroups the keys of one (sequence, head) are split over (tribe_attention_decode_splits): a function of B, heads and n alone."""
+    return int(lib().tribe_attention_decode_splits(B, heads, n))
+
+
+def attention_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n: int, scale: float) -> torch.Tensor:
+    """tribe_attention_decode_fwd: one query row per (sequence, head) against the first n slots of the bf16 caches [B, heads, cap, dim_head]:
+    softmax(scale q K[0:n]^T) V[0:n] -> bf16 [B, heads*dim_head].  q: bf16 [B, >= heads*dim_head] rows whose first heads*dim_head columns
+    are the (rotated) q heads -- the fused qkv buffer of the step serves as it is."""
+    what = "tribe_attention_decode_fwd"
+    B, heads, cap, dim_head = _kv_caches(what, k_cache, v_cache, 4)
+    if dim_head not in DECODE_DIM_HEADS:
+        raise ValueError(f"{what}: dim_head={dim_head} must be one of {DECODE_DIM_HEADS}")
+    _step_rows(what, q, "q", torch.bfloat16, B, heads * dim_head, k_cache.device)
+    if not 1 <= n <= cap:
+        raise ValueError(f"{what}: n={n} keys outside 1 .. capacity {cap}")
+    _cuda(q, torch.bfloat16, "q", contiguous=False)
+    out = torch.empty(B, heads * dim_head, dtype=torch.bfloat16, device=q.device)
+    nbytes = lib().tribe_attention_decode_workspace_bytes(B, heads, dim_head, n)
+    ws = workspace(nbytes, q.device, tag="decode")
+    check(lib().tribe_attention_decode_fwd(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), B, heads, dim_head, cap, n, scale,
+                                           out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), what)
+    return out
+
+
+def _encoder_caches(what: str, pack: EncoderPack, x: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor) -> tuple[int, int]:
+    depth, B, heads, cap, dim_head = _kv_caches(what, k_cache, v_cache, 5)
+    if (depth, heads, dim_head) != (pack.depth, pack.heads, pack.dim_head):
+        raise ValueError(f"{what}: caches {tuple(k_cache.shape)} do not match depth={pack.depth}, heads={pack.heads}, dim_head={pack.dim_head}")
+    if not pack.causal:
+        raise ValueError(f"{what}: the encoder is bidirectional (causal=False): it has no incremental form")
+    if dim_head not in DECODE_DIM_HEADS:
+        raise ValueError(f"{what}: dim_head={dim_head} must be one of {DECODE_DIM_HEADS}")
+    return B, cap
+
+
+def encoder_step(x: torch.Tensor, pack: EncoderPack, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: int,
+                 out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """tribe_encoder_step_fwd: the causal encoder at position `pos`.  x f32 [B, dim] is consumed; the bf16 caches
+    [depth, B, heads, cap, dim_head] hold positions 0 .. pos-1 and receive slot pos; returns final-normed y [B, dim]."""
+    what = "tribe_encoder_step_fwd"
+    B, cap = _encoder_caches(what, pack, x, k_cache, v_cache)
+    _step_rows(what, x, "x", torch.float32, B, pack.dim, k_cache.device)
+    if x.shape[1] != pack.dim or not x.is_contiguous():
+        raise ValueError(f"{what}: x must be contiguous [B={B}, dim={pack.dim}], got shape {tuple(x.shape)}")
+    if not 0 <= pos < cap:
+        raise ValueError(f"{what}: pos={pos} outside the cache capacity {cap}")
+    _cuda(x, torch.float32, "x")
+    d = _encoder_desc(pack, B, 1, *pack.tables(cap, x.device))
+    y = torch.empty(B, pack.dim, dtype=out_dtype, device=x.device)
+    nbytes = lib().tribe_encoder_step_workspace_bytes(C.byref(d), cap)
+    ws = workspace(nbytes, x.device)
+    check(lib().tribe_encoder_step_fwd(C.byref(d), x.data_ptr(), y.data_ptr(), _DT[out_dtype], k_cache.data_ptr(), v_cache.data_ptr(), cap, pos,
+                                       ws.data_ptr(), ws.numel(), _stream()), what)
+    return y
+
+
+def encoder_prefill(x: torch.Tensor, pack: EncoderPack, k_cache: torch.Tensor, v_cache: torch.Tensor, T: int,
+                    out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """tribe_encoder_prefill_fwd: the causal forward over T positions from an empty cache, which also fills slots 0 .. T-1 of the caches.
+    x f32 [B*T, dim] is consumed; returns final-normed y [B*T, dim]."""
+    what = "tribe_encoder_prefill_fwd"
+    B, cap = _encoder_caches(what, pack, x, k_cache, v_cache)
+    if not 1 <= T <= cap:
+        raise ValueError(f"{what}: T={T} positions do not fit the cache capacity {cap}")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.shape != (B * T, pack.dim) or not x.is_contiguous():
+        raise ValueError(f"{what}: x must be a contiguous f32 [B*T={B * T}, dim={pack.dim}] tensor")
+    if x.device != k_cache.device:
+        raise ValueError(f"{what}: x is on {x.device}, the caches on {k_cache.device}")
+    _cuda(x, torch.float32, "x")
+    d = _encoder_desc(pack, B, T, *pack.tables(T, x.device))
+    y = torch.empty(B * T, pack.dim, dtype=out_dtype, device=x.device)
+    nbytes = lib().tribe_encoder_workspace_bytes(C.byref(d))
+    ws = workspace(nbytes, x.device)
+    check(lib().tribe_encoder_prefill_fwd(C.byref(d), x.data_ptr(), y.data_ptr(), _DT[out_dtype], k_cache.data_ptr(), v_cache.data_ptr(), cap,
+                                          ws.data_ptr(), ws.numel(), _stream()), what)
     return y
 
 

@@ -307,6 +307,41 @@ int tribe_encoder_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_
 int tribe_encoder_fwd_ex(const tribe_encoder_desc* d, uint32_t flags, float* x, void* y, int32_t y_dtype,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- streaming a causal encoder one position at a time: KV cache and single-query attention (csrc/attn_decode.hip) ----
+ * A cache is two bf16 tensors K, V [B, heads, cap, dim_head] per layer (cap = capacity in positions): each (sequence, head) owns one
+ * contiguous run of keys.  The encoder entry points take all layers at once: [depth, B, heads, cap, dim_head].
+ *
+ * tribe_kv_append: one position of every sequence.  qkv: the step's fused bf16 [B, 3 * heads * dim_head] rows (q heads | k heads | v heads).
+ *   Rotates the q heads and the k heads in place at position `pos` -- tribe_rotary_fwd's arithmetic, bit for bit; interleaved 0 or 1;
+ *   cos / sin f32 [> pos, rot_dim / 2]; rot_dim == 0: no rotation, tables unused -- and stores the rotated k heads and the v heads into slot
+ *   `pos` of the two caches.  One launch; no other slot is touched.  Buffers 16-byte aligned. */
+int tribe_kv_append(uint16_t* qkv, int64_t B, int32_t heads, int32_t dim_head, int32_t rot_dim, int32_t interleaved,
+                    const float* cos_tab, const float* sin_tab, int64_t pos, uint16_t* k_cache, uint16_t* v_cache, int64_t cap,
+                    void* stream);
+/* tribe_attention_decode_fwd: out[b, h] = softmax(scale * q[b, h] . K[b, h, 0:n]^T) V[b, h, 0:n] for one query row per (b, h), n = pos + 1
+ *   keys, 1 <= n <= cap; dim_head in {64, 128, 192, 384}.  q: bf16, head h of sequence b at q + b * ld_q + h * dim_head (ld_q = 3 * inner
+ *   reads the q heads of a fused row); out: bf16 [B, heads * dim_head].  Softmax in f32, p rounded to bf16 before it multiplies V.  The keys
+ *   of one (b, h) are split over tribe_attention_decode_splits(B, heads, n) workgroups -- a function of these three alone -- whose f32
+ *   (m, l, o) parts travel through the workspace (tribe_attention_decode_workspace_bytes, 256-byte aligned; unused at one split) and are
+ *   summed in split order by a second launch: no atomics, the same call gives the same bits.  Nothing at or beyond slot n is read. */
+int32_t tribe_attention_decode_splits(int64_t B, int32_t heads, int64_t n);
+size_t tribe_attention_decode_workspace_bytes(int64_t B, int32_t heads, int32_t dim_head, int64_t n);
+int tribe_attention_decode_fwd(const uint16_t* q, int64_t ld_q, const uint16_t* k_cache, const uint16_t* v_cache, int64_t B,
+                               int32_t heads, int32_t dim_head, int64_t cap, int64_t n, float scale, uint16_t* out,
+                               void* workspace, size_t workspace_bytes, void* stream);
+/* tribe_encoder_step_fwd: the causal encoder at position `pos` (0 <= pos < cap) given the caches of positions 0 .. pos-1; d->T must be 1,
+ *   x f32 [B, dim] (updated in place), y [B, dim]; d->cos_tab / sin_tab hold at least pos + 1 rows.  Per layer: ScaleNorm, QKV GEMM,
+ *   tribe_kv_append (slot pos), tribe_attention_decode_fwd (n = pos + 1), out-proj + residual, ScaleNorm, FF1 + GELU, FF2 + residual;
+ *   then the final ScaleNorm.  The workspace size depends on the capacity, not on pos. */
+size_t tribe_encoder_step_workspace_bytes(const tribe_encoder_desc* d, int64_t cap);
+int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+                           int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream);
+/* tribe_encoder_prefill_fwd: tribe_encoder_fwd_ex with TRIBE_ENCODER_CAUSAL over d->T <= cap positions from an empty cache (same
+ *   workspace: tribe_encoder_workspace_bytes), which also copies every layer's rotated k heads and v heads into slots 0 .. T-1: one more
+ *   launch per layer. */
+int tribe_encoder_prefill_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+                              int64_t cap, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * a16-a18: building blocks of the frozen extractors (HF transformers architectures)
  * ------------------------------------------------------------------------- */
