@@ -60,11 +60,17 @@ def grad_sums_and_cast(dy: torch.Tensor, M: int, N: int, res: torch.Tensor | Non
 STREAM_K_WGRAD = True
 
 
+def wgrad_reads_transposed(M: int, N: int, K: int, ld_dy: int, ld_x: int) -> bool:
+    """Whether `wgrad` takes the transposed-operand form of the GEMM (stated once; tests/test_autograd_ref_host.py holds the copy in the
+    case table of oracle/autograd_ref.py to it)."""
+    return M % 64 == 0 and N % 8 == 0 and K % 8 == 0 and N >= 128 and K >= 128 and ld_dy % 8 == 0 and ld_x % 8 == 0
+
+
 def wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, M: int, N: int, K: int, ld_dy: int, ld_x: int) -> None:
     """dw[n, k] = sum_m dy[m, n] x[m, k]  (dy bf16 [M, ld_dy >= N], x bf16 [M, ld_x >= K], dw f32 [N, K]): the weight gradient of a Linear.
     Shapes the 256^2 kernel covers go through its transposed-operand form (desc.trans_ab: dy and x are read as they lie, the LDS reads
     transpose); the rest keep the two explicit bf16 transposes in front of the NT GEMM."""
-    if M % 64 == 0 and N % 8 == 0 and K % 8 == 0 and N >= 128 and K >= 128 and ld_dy % 8 == 0 and ld_x % 8 == 0:
+    if wgrad_reads_transposed(M, N, K, ld_dy, ld_x):
         _gemm(dy, x, dw, lda=ld_dy, ldb=ld_x, ldc=K, M=N, N=K, K=M, trans_ab=True, stream_k=STREAM_K_WGRAD)
         return
     dy_t = transpose_bf16(dy, 1, M, N, 0, ld_dy)[0]   # [N, M_pad]
@@ -359,6 +365,9 @@ class ScaleNormFork(torch.autograd.Function):
         y = ops.scalenorm(x, g, gain_scale, eps, torch.bfloat16)
         ctx.save_for_backward(x, g, res_scale)
         ctx.gs, ctx.eps = gain_scale, eps
+        # an unused branch arrives in backward as None, not as a zero tensor: without this line autograd materialised zeros, `dy is None` and
+        # `dxr is None` below were never true, and a residual-only use ran the whole kernel over a zero gradient
+        ctx.set_materialize_grads(False)
         return y, x.view_as(x)
 
     @staticmethod

@@ -34,6 +34,11 @@ Contents
                    under any split of K, and replays of the launcher's stream-K
                    and split-K plans with the case table of the GPU test.
 
+* `autograd_ref` -- float64 statements of the forward and every gradient of the
+                   autograd functions (Linear, QKVLinear, FeedForward, the norms,
+                   VoxelHead, the losses), their case and branch tables, the
+                   bit-exact and per-element bounded criteria, and emulated faults.
+
 Pinning status (see DESIGN.md "Oracle")
 ---------------------------------------
 * Everything that lives in the reference's own files (SubjectLayers,
