@@ -552,6 +552,19 @@ class EncoderStream:
         return model.predictor.forward_tokens(y.view(B, 1, -1), data["subject_id"])[:, :, 0]
 
     @torch.no_grad()
+    def push_block(self, data: SegmentData | dict) -> torch.Tensor:
+        """The next k stimulus steps of every timeline at once, onto a stream that holds any number of steps: each modality [B, L, D, k] or
+        [B, D, k], plus `subject_id` -> f32 [B, n_outputs, k], the predictions at steps pos .. pos+k-1.  What k calls of `push` give (to
+        rounding), with every GEMM and one attention launch per layer run once for the block (HipEncoder.extend)."""
+        model = self.model
+        data = model._batch_dict(data)
+        k = self._steps("push_block", data, one=False)
+        x, B, _ = model._fused_embed(data, add_embeddings=True, pos0=self.cache.pos, draw=False)   # positional rows pos .. pos+k-1
+        model.encoder._check_stream("extend", x.view(B, k, -1), self.cache, k)
+        y = model.encoder.extend_tokens(x, B, k, self.cache, torch.bfloat16)
+        return model.predictor.forward_tokens(y.view(B, k, -1), data["subject_id"])
+
+    @torch.no_grad()
     def prefill(self, data: SegmentData | dict) -> torch.Tensor:
         """The first T0 steps at once, into an empty stream: each modality [B, L, D, T0] or [B, D, T0] -> f32 [B, n_outputs, T0]; `push`
         continues at step T0."""

@@ -61,7 +61,12 @@ __device__ __forceinline__ int swz_chunk(int chunk, int row) {
 
 // CAUSAL: key <= query (HF LlamaAttention.is_causal, modeling_llama.py); a wave skips key tiles that lie entirely
 // above its 16 query rows, the workgroup stops at the last tile its 128 rows can see.
-template <int DH, int CAUSAL, int RELKEY>
+// EXTEND: the block-append form of the causal kernel (tribe_attention_extend_fwd).  T = a.T query rows per (sequence, head) at positions
+// pos .. pos + T - 1 (row b * T + t of the q buffer) see keys j <= pos + t of a KV cache [B, heads, cap, DH] that holds Tk = pos + T keys:
+// K / V rows come from a.k / a.v + b * kv_stride_b + hk * kv_stride_h, ld_kv apart, through the same staging.  Every place the mask lives
+// takes the query's POSITION (qp0 = pos + q0) where the square form takes its row, and the key count Tk where it takes T; with EXTEND = 0
+// pos is the constant 0 and Tk is T, so the square instantiations compile to what they were.  No cache slot at or beyond Tk is read.
+template <int DH, int CAUSAL, int RELKEY, int EXTEND = 0>
 __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
   using C = AttnCfg<DH>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -69,7 +74,10 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fq = lane >> 4, l15 = lane & 15;
 
-  const int T = a.T;
+  static_assert(!EXTEND || (CAUSAL && !RELKEY), "the block-append form is causal and has no relative_key bias");
+  const int T = a.T;                          // query rows per (sequence, head)
+  const int pos = EXTEND ? a.pos : 0;         // position of query row 0
+  const int Tk = EXTEND ? a.pos + a.T : T;    // keys
   const float scale_log2e = a.scale_log2e;
   // Workgroups are dealt to the 8 XCDs round-robin by id, and each XCD has its own L2.  All query blocks of one (sequence,
   // head) pair read the same K / V (1.5 MiB at T = 1024, DH = 384): keep them on ONE XCD -- id % 8 picks the XCD, the ids that
@@ -84,11 +92,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
   const int hk = h / a.group;
   const int64_t ld = a.ld_kv;
   const unsigned short* qbase = a.q + (int64_t)b * T * a.ld_q + (int64_t)h * DH;
-  const unsigned short* kbase = a.k + (int64_t)b * T * ld + (int64_t)hk * DH;
-  const unsigned short* vbase = a.v + (int64_t)b * T * ld + (int64_t)hk * DH;
+  const unsigned short* kbase = EXTEND ? a.k + (int64_t)b * a.kv_stride_b + (int64_t)hk * a.kv_stride_h : a.k + (int64_t)b * T * ld + (int64_t)hk * DH;
+  const unsigned short* vbase = EXTEND ? a.v + (int64_t)b * a.kv_stride_b + (int64_t)hk * a.kv_stride_h : a.v + (int64_t)b * T * ld + (int64_t)hk * DH;
 
   // ---- Q^T fragments: lane (q = l15, fq) holds Q[q][32 ks + 8 fq .. +7] for every k-step ----
   const int q0 = qb * 128 + wave * 16;
+  const int qp0 = pos + q0;                   // position of this wave's first query row
   const int qrow = (q0 + l15 < T) ? q0 + l15 : T - 1;
   bf16x8_t qf[C::KS];
 #pragma unroll
@@ -109,14 +118,14 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
     char* kdst = smem + buf * 2 * C::TILE_BYTES;
     const unsigned short* kb = kbase + (int64_t)key0 * ld;
     const unsigned short* vb = vbase + (int64_t)key0 * ld;
-    const bool full = key0 + C::KV <= T;
+    const bool full = key0 + C::KV <= Tk;
 #pragma unroll
     for (int i = 0; i < C::PPW; ++i) {
       const int piece = wave + C::WAVES * i;  // wave-uniform
       if (piece < C::PIECES) {
         int off = st_off[i];
         if (!full) {  // tail keys re-read a valid row; they are masked to -inf below
-          const int row = (key0 + st_row[i] < T) ? st_row[i] : T - 1 - key0;
+          const int row = (key0 + st_row[i] < Tk) ? st_row[i] : Tk - 1 - key0;
           off = row * (int)ld + st_src[i];
         }
         glds16(kb + off, lds_addr(kdst + piece * 1024));
@@ -157,8 +166,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = (short)0x3F80;
 
-  int kv_end = T;  // keys this workgroup can see
-  if (CAUSAL) { const int last_q = qb * 128 + 127; kv_end = (last_q + 1 < T) ? last_q + 1 : T; }
+  int kv_end = Tk;  // keys this workgroup can see
+  if (CAUSAL) { const int last_q = pos + qb * 128 + 127; kv_end = (last_q + 1 < Tk) ? last_q + 1 : Tk; }
   const int ntiles = (kv_end + C::KV - 1) / C::KV;
   // LDS-DMA loads issued by this wave per staged tile (K and V pieces): the 3-slot pipeline leaves exactly one tile in flight
   int my_glds = 0;
@@ -180,16 +189,16 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
     if (C::NBUF == 2 && t + 1 < ntiles) stage(cur ^ 1, (t + 1) * C::KV);
     const char* kt = smem + cur * 2 * C::TILE_BYTES;
     const char* vt = kt + C::TILE_BYTES;
-    if (!CAUSAL || t * C::KV <= q0 + 15) {  // wave-uniform: some key of this tile is visible to some row of this wave
+    if (!CAUSAL || t * C::KV <= qp0 + 15) {  // wave-uniform: some key of this tile is visible to some row of this wave
 
     // ---- S^T[key][q] = sum_d K[key][d] Q[q][d]: per 32-key sub-tile two accumulators (keys 0-15, 16-31) share each Q fragment ----
     float sv[C::NSUB][8];
     float pmax = -INFINITY;
-    const int lim = CAUSAL ? ((q0 + l15 + 1 < T) ? q0 + l15 + 1 : T) : T;  // first masked key for this lane's query
+    const int lim = CAUSAL ? ((qp0 + l15 + 1 < Tk) ? qp0 + l15 + 1 : Tk) : Tk;  // first masked key for this lane's query
 #pragma unroll
     for (int u = 0; u < C::NSUB; ++u) {
       const int sub_key0 = t * C::KV + u * 32;
-      if (sub_key0 >= T || (CAUSAL && sub_key0 > q0 + 15)) {  // wave-uniform: nothing visible in this sub-tile
+      if (sub_key0 >= Tk || (CAUSAL && sub_key0 > qp0 + 15)) {  // wave-uniform: nothing visible in this sub-tile
 #pragma unroll
         for (int j = 0; j < 8; ++j) sv[u][j] = -INFINITY;
         continue;
@@ -219,7 +228,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
       // sv keeps the RAW scores: the softmax scale rides in the exponent's fma below (scale > 0, so the maximum commutes with it).
       // Only a sub-tile that crosses the end of the sequence or the causal diagonal of this wave's rows pays for masking
       // (wave-uniform test; the per-element compare + select was a quarter of the loop's vector instructions at DH = 64).
-      const bool edge = sub_key0 + 32 > T || (CAUSAL && sub_key0 + 31 > q0);
+      const bool edge = sub_key0 + 32 > Tk || (CAUSAL && sub_key0 + 31 > qp0);
       if (edge) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -271,7 +280,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
 #pragma unroll
     for (int u = 0; u < C::NSUB; ++u) {
       const int sub_key0 = t * C::KV + u * 32;
-      if (sub_key0 >= T || (CAUSAL && sub_key0 > q0 + 15)) continue;  // P is all zero there
+      if (sub_key0 >= Tk || (CAUSAL && sub_key0 > qp0 + 15)) continue;  // P is all zero there
       if (LSUM_MFMA) lacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[u], lacc, 0, 0, 0);
 #pragma unroll
       for (int dt = 0; dt < C::DT; ++dt) {
@@ -940,7 +949,52 @@ int launch_attn(const AttnArgs& a, int64_t B, hipStream_t s) {
   return 0;
 }
 
+// the block-append form: same grid walk (all query blocks of one (sequence, head) on one XCD), same LDS, T = a.T queries per pair
+template <int DH>
+int launch_attn_extend(const AttnArgs& a, int64_t B, hipStream_t s) {
+  using C = AttnCfg<DH>;
+  raise_dynamic_lds_once<attn_fwd_kernel<DH, 1, 0, 1>>(C::SMEM);
+  const int64_t nblocks = (B * a.heads_q + 7) / 8 * 8 * a.qblocks;
+  if (nblocks >= (1ll << 31)) { tribe_set_error("tribe_attention_extend_fwd: grid too large"); return -1; }
+  hipLaunchKernelGGL((attn_fwd_kernel<DH, 1, 0, 1>), dim3((unsigned)nblocks), dim3(512), C::SMEM, s, a);
+  TRIBE_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int tribe_attention_extend_fwd(const uint16_t* q, int64_t ld_q, const uint16_t* k_cache, const uint16_t* v_cache, int64_t B,
+                                          int32_t heads, int32_t dim_head, int64_t cap, int64_t pos, int64_t k, float scale, uint16_t* out,
+                                          void* stream) {
+  TRIBE_REQUIRE(q && k_cache && v_cache && out, "tribe_attention_extend_fwd: null pointer");
+  TRIBE_REQUIRE(B > 0 && heads > 0, "tribe_attention_extend_fwd: bad shape (B=%lld, heads=%d)", (long long)B, heads);
+  TRIBE_REQUIRE(dim_head == 64 || dim_head == 128 || dim_head == 192 || dim_head == 384,
+                "tribe_attention_extend_fwd: dim_head=%d not in {64,128,192,384}", dim_head);
+  TRIBE_REQUIRE(k >= 1 && pos >= 0 && cap < (1ll << 31) && pos + k <= cap,
+                "tribe_attention_extend_fwd: k=%lld positions from pos=%lld outside the cache capacity %lld (k >= 1, pos >= 0, pos + k <= cap)",
+                (long long)k, (long long)pos, (long long)cap);
+  TRIBE_REQUIRE(ld_q >= (int64_t)heads * dim_head && ld_q % 8 == 0,
+                "tribe_attention_extend_fwd: ld_q=%lld must cover heads * dim_head and be a multiple of 8", (long long)ld_q);
+  TRIBE_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0 && ((uintptr_t)out % 8) == 0,
+                "tribe_attention_extend_fwd: q and the caches must be 16-byte aligned, out 8-byte aligned");
+  AttnArgs a{};
+  a.q = q; a.k = k_cache; a.v = v_cache; a.out = out;
+  a.ld_q = ld_q; a.ld_kv = dim_head; a.ld_out = (int64_t)heads * dim_head;
+  a.kv_stride_b = (int64_t)heads * cap * dim_head; a.kv_stride_h = cap * dim_head;
+  a.T = (int)k; a.pos = (int)pos; a.heads_q = heads; a.group = 1;
+  a.scale_log2e = scale * 1.4426950408889634f;
+  a.qblocks = (int)((k + 127) / 128);
+  a.n_bh = (int)(B * heads);
+  TRIBE_REQUIRE(B * heads < (1ll << 31), "tribe_attention_extend_fwd: B * heads too large");
+  hipStream_t s = (hipStream_t)stream;
+  switch (dim_head) {
+    case 64: return launch_attn_extend<64>(a, B, s);
+    case 128: return launch_attn_extend<128>(a, B, s);
+    case 192: return launch_attn_extend<192>(a, B, s);
+    default: return launch_attn_extend<384>(a, B, s);
+  }
+}
+
 int tribe_internal_attn_d64_launch(const void* args, int64_t B, int relkey, int variant, hipStream_t s);   // attention_d64.hip
 namespace {
 

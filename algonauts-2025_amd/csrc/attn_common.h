@@ -45,6 +45,10 @@ struct AttnArgs {
   // tables f32 [T, rot_dim / 2]; nullptr = q arrives rotated.  Same arithmetic, same bf16 rounding as rotary_kernel.
   const float* q_cos; const float* q_sin; int q_rot_dim;
   float* lse;   // optional [B, heads_q, T] base-2 log-sum-exp of the scaled scores (DH = 384 one-wave kernel only; nullptr = not wanted)
+  // block-append form of the 16-row kernel only (attn_fwd_kernel<.., EXTEND = 1>): T queries at positions pos .. pos + T - 1 against keys
+  // 0 .. pos + T - 1 of a KV cache -- K / V of (b, hk) start at k + b * kv_stride_b + hk * kv_stride_h (elements), rows ld_kv apart
+  int64_t kv_stride_b, kv_stride_h;
+  int pos;
 };
 
 // compile-time loop: the accumulator tile index selects literal registers (attn_acc_regs.h)

@@ -2,8 +2,9 @@
 //
 // Cache: per layer two bf16 tensors K, V [B, heads, cap, dim_head] -- every (sequence, head) owns one contiguous run of keys, so a step's
 // attention streams 2 * n * dim_head * 2 bytes per head front to back.
-//   kv_append_kernel  one position: rotates the q heads (in place) and the k heads of a fused qkv row with rotary_kernel's arithmetic
-//                     (rotary_pairs.h) and stores k and v into slot `pos`.
+//   kv_append_kernel  T positions per sequence (a step: T = 1; a block append: T = k): rotates the q heads (in place) and the k heads of
+//                     the fused qkv row b * T + t at position pos + t with rotary_kernel's arithmetic (rotary_pairs.h) and stores k and v
+//                     into slot pos + t.
 //   kv_fill_kernel    a prefill's T positions: copies the already rotated k heads and the v heads of a fused [B*T, 3*inner] buffer into
 //                     slots 0 .. T-1.
 //   attn_decode_split_kernel<DH> / attn_decode_combine_kernel   out = softmax(scale q K[0:n]^T) V[0:n] per (b, h).
@@ -28,22 +29,23 @@ constexpr float DECODE_M_EMPTY = -1.0e30f;   // running maximum of a part that h
 constexpr int DECODE_MAX_SPLITS = 32;
 constexpr int DECODE_MIN_KEYS = 64;          // keys per split at least: one pass of the four waves at U = 2
 
-__global__ __launch_bounds__(256) void kv_append_kernel(unsigned short* __restrict__ qkv, int64_t B, int heads, int dim_head, int rot_dim,
-                                                        int interleaved, const float* __restrict__ cos_tab,
-                                                        const float* __restrict__ sin_tab, int64_t pos, unsigned short* __restrict__ kc,
+__global__ __launch_bounds__(256) void kv_append_kernel(unsigned short* __restrict__ qkv, int64_t B, int64_t T, int heads, int dim_head,
+                                                        int rot_dim, int interleaved, const float* __restrict__ cos_tab,
+                                                        const float* __restrict__ sin_tab, int64_t pos0, unsigned short* __restrict__ kc,
                                                         unsigned short* __restrict__ vc, int64_t cap) {
   const int half = rot_dim >> 1;
   const int items_per_head = dim_head >> 3;   // 8 elements each
   const int rot_items = rot_dim >> 3;
   const int64_t inner = (int64_t)heads * dim_head;
-  const int64_t total = B * 3 * heads * items_per_head;
+  const int64_t total = B * T * 3 * heads * items_per_head;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     int64_t t = idx;
     const int it = (int)(t % items_per_head); t /= items_per_head;
     const int hh = (int)(t % (3 * heads));
-    const int64_t b = t / (3 * heads);
+    const int64_t row = t / (3 * heads);                // b * T + step
+    const int64_t b = row / T, pos = pos0 + (row - b * T);
     const int sec = hh / heads, h = hh - sec * heads;   // 0 q, 1 k, 2 v
-    unsigned short* base = qkv + b * 3 * inner + (int64_t)hh * dim_head;
+    unsigned short* base = qkv + row * 3 * inner + (int64_t)hh * dim_head;
     unsigned short* slot = (sec == 1 ? kc : vc) + ((b * heads + h) * cap + pos) * dim_head;
     if (sec == 2 || it >= rot_items) {   // not rotated: v, and the tail of q / k
       if (sec != 0) *(u16x8_t*)(slot + it * 8) = *(const u16x8_t*)(base + it * 8);
@@ -282,7 +284,30 @@ extern "C" int tribe_kv_append(uint16_t* qkv, int64_t B, int32_t heads, int32_t 
                     ((uintptr_t)cos_tab % 16) == 0 && ((uintptr_t)sin_tab % 16) == 0,
                 "tribe_kv_append: buffers must be 16-byte aligned");
   const int64_t total = B * 3 * heads * (dim_head / 8);
-  hipLaunchKernelGGL(kv_append_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, qkv, B, heads, dim_head, rot_dim,
+  hipLaunchKernelGGL(kv_append_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, qkv, B, (int64_t)1, heads, dim_head,
+                     rot_dim, interleaved, cos_tab, sin_tab, pos, k_cache, v_cache, cap);
+  TRIBE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tribe_kv_append_block(uint16_t* qkv, int64_t B, int64_t k, int32_t heads, int32_t dim_head, int32_t rot_dim,
+                                     int32_t interleaved, const float* cos_tab, const float* sin_tab, int64_t pos, uint16_t* k_cache,
+                                     uint16_t* v_cache, int64_t cap, void* stream) {
+  TRIBE_REQUIRE(qkv && k_cache && v_cache, "tribe_kv_append_block: null pointer");
+  TRIBE_REQUIRE(B > 0 && heads > 0 && dim_head > 0 && dim_head % 8 == 0,
+                "tribe_kv_append_block: bad shape (B=%lld, heads=%d, dim_head=%d; dim_head %% 8 == 0)", (long long)B, heads, dim_head);
+  TRIBE_REQUIRE(k >= 1 && pos >= 0 && pos + k <= cap,
+                "tribe_kv_append_block: k=%lld positions from pos=%lld outside the cache capacity %lld (k >= 1, pos >= 0, pos + k <= cap)",
+                (long long)k, (long long)pos, (long long)cap);
+  TRIBE_REQUIRE(rot_dim >= 0 && rot_dim <= dim_head && rot_dim % 8 == 0,
+                "tribe_kv_append_block: rot_dim=%d must be a multiple of 8 and <= dim_head=%d", rot_dim, dim_head);
+  TRIBE_REQUIRE(rot_dim == 0 || (cos_tab && sin_tab), "tribe_kv_append_block: rotary tables missing");
+  TRIBE_REQUIRE(interleaved == 0 || interleaved == 1, "tribe_kv_append_block: interleaved must be 0 or 1");
+  TRIBE_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0 &&
+                    ((uintptr_t)cos_tab % 16) == 0 && ((uintptr_t)sin_tab % 16) == 0,
+                "tribe_kv_append_block: buffers must be 16-byte aligned");
+  const int64_t total = B * k * 3 * heads * (dim_head / 8);
+  hipLaunchKernelGGL(kv_append_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, qkv, B, k, heads, dim_head, rot_dim,
                      interleaved, cos_tab, sin_tab, pos, k_cache, v_cache, cap);
   TRIBE_LAUNCH_CHECK();
   return 0;

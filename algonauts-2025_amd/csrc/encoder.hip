@@ -442,6 +442,95 @@ extern "C" int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, voi
   return tribe_scalenorm_fwd(x, M, dim, d->final_norm_g, d->norm_gain_scale, d->norm_eps, y, y_dtype, stream);
 }
 
+// ---- block append: d->T = k positions per sequence onto caches that hold `pos` (attention.hip: tribe_attention_extend_fwd) ----
+namespace {
+struct ExtendLayout {
+  int64_t M, inner;
+  uint16_t* xn;     // [B*k, dim] bf16 input of QKV / FF1
+  uint16_t* qkv;    // [B*k, 3*inner]
+  uint16_t* ao;     // [B*k, inner], behind qkv
+  uint16_t* hbuf;   // [B*k, ff_inner], over qkv | ao (dead by then)
+  void* split_ws; size_t split_bytes;
+};
+inline ExtendLayout extend_layout(const tribe_encoder_desc* d, Arena& ws) {
+  ExtendLayout p;
+  const int64_t M = p.M = d->B * d->T, inner = p.inner = (int64_t)d->heads * d->dim_head;
+  p.xn = ws.take<uint16_t>((size_t)M * d->dim * 2);
+  const int64_t wide = (4 * inner > d->ff_inner) ? 4 * inner : d->ff_inner;
+  p.qkv = p.hbuf = ws.take<uint16_t>((size_t)M * wide * 2);
+  p.ao = p.qkv + (size_t)M * 3 * inner;
+  // few rows: the GEMMs may run split over K, as in encoder_fwd_body
+  const int64_t widest = 3 * inner > d->ff_inner ? (3 * inner > d->dim ? 3 * inner : d->dim) : (d->ff_inner > d->dim ? d->ff_inner : d->dim);
+  p.split_bytes = M <= 512 ? align256((size_t)8 * M * widest * 4) : 0;
+  p.split_ws = p.split_bytes ? ws.take<void>(p.split_bytes) : nullptr;
+  return p;
+}
+}  // namespace
+
+extern "C" size_t tribe_encoder_extend_workspace_bytes(const tribe_encoder_desc* d, int64_t cap) {
+  if (!d || d->B <= 0 || d->T <= 0 || cap <= 0) return 0;
+  Arena ws;
+  extend_layout(d, ws);
+  return ws.off;
+}
+
+extern "C" int tribe_encoder_extend_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache,
+                                        uint16_t* v_cache, int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_extend_fwd: null descriptor");
+  TRIBE_REQUIRE(d->T >= 1 && cap > 0 && pos >= 0 && pos + d->T <= cap,
+                "tribe_encoder_extend_fwd: k=%lld positions from pos=%lld outside the cache capacity %lld (k >= 1, pos >= 0, pos + k <= cap)",
+                (long long)d->T, (long long)pos, (long long)cap);
+  TRIBE_REQUIRE(tribe_internal_attention_fused_supported(d->dim_head), "tribe_encoder_extend_fwd: dim_head=%d not in {64,128,192,384}",
+                d->dim_head);
+  int rc = enc_validate(d);
+  if (rc) return rc;
+  TRIBE_REQUIRE(x && y && workspace && k_cache && v_cache, "tribe_encoder_extend_fwd: null pointer");
+  TRIBE_REQUIRE(((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0, "tribe_encoder_extend_fwd: caches must be 16-byte aligned");
+  TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "tribe_encoder_extend_fwd: workspace must be 256-byte aligned");
+  Arena ws(workspace);
+  const ExtendLayout p = extend_layout(d, ws);
+  TRIBE_REQUIRE(workspace_bytes >= ws.off, "tribe_encoder_extend_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+  const int64_t M = p.M, inner = p.inner, dim = d->dim;
+  const int64_t per_layer = d->B * inner * cap;
+  const float scale = 1.0f / sqrtf((float)d->dim_head);
+  // tribe_encoder_step_fwd's launches with k rows per sequence: every ScaleNorm its own launch, one GEMM each, and between QKV and
+  // out-proj the block's rotary + cache write (one launch) and the rectangular causal attention against the cache plus the block
+  for (int l = 0; l < d->depth; ++l) {
+    const tribe_encoder_layer& L = d->layers_host[l];
+    TRIBE_REQUIRE(L.attn_norm_g && L.w_qkv && L.w_out && L.ff_norm_g && L.w_ff1 && L.b_ff1 && L.w_ff2 && L.b_ff2,
+                  "tribe_encoder_extend_fwd: layer %d has a null parameter", l);
+    rc = tribe_scalenorm_fwd(x, M, dim, L.attn_norm_g, d->norm_gain_scale, d->norm_eps, p.xn, TRIBE_BF16, stream);
+    if (rc) return rc;
+    tribe_gemm_desc g = Linear(TRIBE_ROLE_QKV, M, p.xn, dim, L.w_qkv, nullptr, p.qkv, 3 * inner, TRIBE_BF16);
+    allow_split_k(g, p.split_ws, p.split_bytes);
+    rc = tribe_gemm_bf16(&g, stream);
+    if (rc) return rc;
+    uint16_t *kc = k_cache + l * per_layer, *vc = v_cache + l * per_layer;
+    rc = tribe_kv_append_block(p.qkv, d->B, d->T, d->heads, d->dim_head, d->rot_dim, d->rotary_interleaved, d->cos_tab, d->sin_tab, pos, kc, vc,
+                               cap, stream);
+    if (rc) return rc;
+    rc = tribe_attention_extend_fwd(p.qkv, 3 * inner, kc, vc, d->B, d->heads, d->dim_head, cap, pos, d->T, scale, p.ao, stream);
+    if (rc) return rc;
+    g = Linear(TRIBE_ROLE_OUT_PROJ, M, p.ao, inner, L.w_out, nullptr, x, dim, TRIBE_F32).residual(x);
+    g.res_scale = L.attn_res_scale;
+    allow_split_k(g, p.split_ws, p.split_bytes);
+    rc = tribe_gemm_bf16(&g, stream);
+    if (rc) return rc;
+    rc = tribe_scalenorm_fwd(x, M, dim, L.ff_norm_g, d->norm_gain_scale, d->norm_eps, p.xn, TRIBE_BF16, stream);
+    if (rc) return rc;
+    g = Linear(TRIBE_ROLE_FF1, M, p.xn, dim, L.w_ff1, L.b_ff1, p.hbuf, d->ff_inner, TRIBE_BF16).activation(TRIBE_ACT_GELU);
+    allow_split_k(g, p.split_ws, p.split_bytes);
+    rc = tribe_gemm_bf16(&g, stream);
+    if (rc) return rc;
+    g = Linear(TRIBE_ROLE_FF2, M, p.hbuf, d->ff_inner, L.w_ff2, L.b_ff2, x, dim, TRIBE_F32).residual(x);
+    g.res_scale = L.ff_res_scale;
+    allow_split_k(g, p.split_ws, p.split_bytes);
+    rc = tribe_gemm_bf16(&g, stream);
+    if (rc) return rc;
+  }
+  return tribe_scalenorm_fwd(x, M, dim, d->final_norm_g, d->norm_gain_scale, d->norm_eps, y, y_dtype, stream);
+}
+
 extern "C" int tribe_voxel_head_fwd(const uint16_t* x, int64_t B, int64_t T, int64_t C_pad, const uint16_t* w_packed, int64_t S,
                                     int64_t V, int64_t V_pad, const float* bias, const int64_t* subjects, float* y, void* stream) {
   TRIBE_REQUIRE(x && w_packed && subjects && y, "tribe_voxel_head_fwd: null pointer");

@@ -30,7 +30,9 @@ A causal encoder can also be followed one position at a time: `new_cache(batch_s
 rotated keys and values, bf16 [depth, B, heads, max_len, dim_head]), `step(x[B, dim], cache)` gives the output at position `cache.pos` from
 one row per GEMM and a single-query attention against the cache (tribe_encoder_step_fwd: tribe_kv_append + tribe_attention_decode_fwd per
 layer, csrc/attn_decode.hip), and `prefill(x[B, T0, dim], cache)` is the causal forward over the first T0 positions that also fills the
-cache (tribe_encoder_prefill_fwd).  Inference only, like `forward`.
+cache (tribe_encoder_prefill_fwd).  `extend(x[B, k, dim], cache)` appends a block of k positions to a cache that holds any number of them
+(tribe_encoder_extend_fwd: k rows per sequence through every GEMM, tribe_kv_append_block, and the rectangular causal flash kernel
+tribe_attention_extend_fwd, csrc/attention.hip, against the cache plus the block itself).  Inference only, like `forward`.
 """
 
 from __future__ import annotations
@@ -279,6 +281,28 @@ class HipEncoder(nn.Module):
         self._check_stream("step", x, cache, 1)
         x2d = x.detach().to(torch.float32).clone().contiguous()
         return self.step_tokens(x2d, cache, torch.float32)
+
+    def extend_tokens(self, x2d: torch.Tensor, B: int, k: int, cache: EncoderCache, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+        """x2d f32 [B*k, dim] (row b*k + t), CONSUMED -> y [B*k, dim] at positions cache.pos .. cache.pos+k-1; cache.pos advances by k."""
+        y = ops.encoder_extend(x2d, self.packed(), cache.k, cache.v, cache.pos, k, out_dtype)
+        cache.pos += k
+        return y
+
+    def extend(self, x: torch.Tensor, cache: EncoderCache) -> torch.Tensor:
+        """x [B, k, dim], the encoder inputs at positions cache.pos .. cache.pos+k-1 -> y [B, k, dim], the outputs there: equal (to rounding)
+        to those rows of `forward` on the whole sequence so far.  The block goes through every GEMM once (k rows per sequence) and through
+        one attention launch per layer against the cache plus itself (tribe_encoder_extend_fwd), where k calls of `step` would stream the
+        weights and pay the launches k times.  The cache may be empty (a prefill through this route) or hold any number of positions.
+        Advances cache.pos by k.  Inference only, like `forward` / `forward_tokens`: eval semantics, none of attn_dropout, ff_dropout,
+        layer_dropout."""
+        if x.ndim != 3:
+            raise ValueError(f"HipEncoder.extend: expected [B, k, dim], got {tuple(x.shape)}")
+        B, k, D = x.shape
+        self._check_stream("extend", x, cache, k)
+        if k < 1:
+            raise ValueError("HipEncoder.extend: k must be at least 1")
+        x2d = x.detach().to(torch.float32).reshape(B * k, D).clone()
+        return self.extend_tokens(x2d, B, k, cache, torch.float32).view(B, k, D)
 
 
 class TransformerEncoderConfig(pydantic.BaseModel):

@@ -293,6 +293,10 @@ SIGNATURES = {
     "tribe_encoder_step_workspace_bytes": (sz, [C.POINTER(EncoderDesc), i64]),
     "tribe_encoder_step_fwd": (C.c_int, [C.POINTER(EncoderDesc), vp, vp, i32, vp, vp, i64, i64, vp, sz, vp]),
     "tribe_encoder_prefill_fwd": (C.c_int, [C.POINTER(EncoderDesc), vp, vp, i32, vp, vp, i64, vp, sz, vp]),
+    "tribe_kv_append_block": (C.c_int, [vp, i64, i64, i32, i32, i32, i32, vp, vp, i64, vp, vp, i64, vp]),
+    "tribe_attention_extend_fwd": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, i64, i64, i64, f32, vp, vp]),
+    "tribe_encoder_extend_workspace_bytes": (sz, [C.POINTER(EncoderDesc), i64]),
+    "tribe_encoder_extend_fwd": (C.c_int, [C.POINTER(EncoderDesc), vp, vp, i32, vp, vp, i64, i64, vp, sz, vp]),
     "tribe_voxel_head_fwd": (C.c_int, [vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp]),
     "tribe_adaptive_avg_pool_fwd": (C.c_int, [vp, i64, i64, vp, i64, vp]),
     "tribe_mse_fwd": (C.c_int, [vp, vp, i64, vp, vp, sz, vp]),

@@ -896,6 +896,84 @@ def encoder_prefill(x: torch.Tensor, pack: EncoderPack, k_cache: torch.Tensor, v
     return y
 
 
+# ---- block append: k positions at once onto a cache that holds `pos` ----
+def _block_rows(what: str, t: torch.Tensor, name: str, dtype: torch.dtype, B: int, k: int, width: int, exact: bool, device: torch.device) -> None:
+    """A block's rows [B*k, width] (row b*k + t = step t of sequence b), checked before any device work."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(t)}")
+    if t.dtype != dtype:
+        raise TypeError(f"{what}: {name} must be {dtype}, got {t.dtype}")
+    if t.ndim != 2 or t.shape[0] != B * k or t.stride(1) != 1 or (t.shape[1] != width if exact else t.shape[1] < width) \
+            or (exact and not t.is_contiguous()):
+        shape = f"contiguous [B*k={B * k}, {width}]" if exact else f"[B*k={B * k}, >= {width}] with unit column stride"
+        raise ValueError(f"{what}: {name} must be {shape}, got shape {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{what}: {name} is on {t.device}, the caches on {device}")
+
+
+def _block_range(what: str, pos: int, k: int, cap: int) -> None:
+    if k < 1:
+        raise ValueError(f"{what}: k={k} must be at least 1")
+    if pos < 0 or pos + k > cap:
+        raise ValueError(f"{what}: positions pos={pos} .. pos+k={pos + k} outside the cache capacity {cap}")
+
+
+def kv_append_block(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: int, k: int, rot_dim: int, cos: torch.Tensor | None,
+                    sin: torch.Tensor | None, interleaved: bool) -> torch.Tensor:
+    """tribe_kv_append_block: kv_append for k rows per sequence.  Rotates the q and k heads of the fused bf16 qkv [B*k, 3*heads*dim_head] in
+    place, row b*k + t at position pos + t (ops.rotary_'s bits; cos / sin f32 [>= pos+k, rot_dim/2], unused at rot_dim == 0), and stores the
+    rotated k heads and the v heads into slots pos .. pos+k-1 of the bf16 caches [B, heads, cap, dim_head].  Returns qkv."""
+    what = "tribe_kv_append_block"
+    B, heads, cap, dim_head = _kv_caches(what, k_cache, v_cache, 4)
+    _block_range(what, pos, k, cap)
+    _block_rows(what, qkv, "qkv", torch.bfloat16, B, k, 3 * heads * dim_head, True, k_cache.device)
+    if rot_dim:
+        for name, t in (("cos", cos), ("sin", sin)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 2 or t.shape[1] != rot_dim // 2 or t.shape[0] < pos + k \
+                    or not t.is_contiguous() or t.device != k_cache.device:
+                raise ValueError(f"{what}: {name} must be a contiguous f32 [>= pos+k={pos + k}, rot_dim/2={rot_dim // 2}] table on {k_cache.device}")
+    _cuda(qkv, torch.bfloat16, "qkv")
+    check(lib().tribe_kv_append_block(qkv.data_ptr(), B, k, heads, dim_head, rot_dim, int(interleaved), _p(cos) if rot_dim else None,
+                                      _p(sin) if rot_dim else None, pos, k_cache.data_ptr(), v_cache.data_ptr(), cap, _stream()), what)
+    return qkv
+
+
+def attention_extend(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: int, k: int, scale: float) -> torch.Tensor:
+    """tribe_attention_extend_fwd: k query rows per (sequence, head) at positions pos .. pos+k-1 against the first pos+k slots of the bf16
+    caches [B, heads, cap, dim_head], query t under the mask key <= pos + t -> bf16 [B*k, heads*dim_head].  q: bf16 [B*k, >= heads*dim_head]
+    rows (row b*k + t) whose first heads*dim_head columns are the rotated q heads -- the block's fused qkv buffer serves as it is.  The
+    caches must already hold the block's own slots (kv_append_block)."""
+    what = "tribe_attention_extend_fwd"
+    B, heads, cap, dim_head = _kv_caches(what, k_cache, v_cache, 4)
+    if dim_head not in DECODE_DIM_HEADS:
+        raise ValueError(f"{what}: dim_head={dim_head} must be one of {DECODE_DIM_HEADS}")
+    _block_range(what, pos, k, cap)
+    _block_rows(what, q, "q", torch.bfloat16, B, k, heads * dim_head, False, k_cache.device)
+    _cuda(q, torch.bfloat16, "q", contiguous=False)
+    out = torch.empty(B * k, heads * dim_head, dtype=torch.bfloat16, device=q.device)
+    check(lib().tribe_attention_extend_fwd(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), B, heads, dim_head, cap, pos, k,
+                                           scale, out.data_ptr(), _stream()), what)
+    return out
+
+
+def encoder_extend(x: torch.Tensor, pack: EncoderPack, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: int, k: int,
+                   out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """tribe_encoder_extend_fwd: the causal encoder at positions pos .. pos+k-1.  x f32 [B*k, dim] (row b*k + t) is consumed; the bf16
+    caches [depth, B, heads, cap, dim_head] hold positions 0 .. pos-1 and receive slots pos .. pos+k-1; returns final-normed y [B*k, dim]."""
+    what = "tribe_encoder_extend_fwd"
+    B, cap = _encoder_caches(what, pack, x, k_cache, v_cache)
+    _block_range(what, pos, k, cap)
+    _block_rows(what, x, "x", torch.float32, B, k, pack.dim, True, k_cache.device)
+    _cuda(x, torch.float32, "x")
+    d = _encoder_desc(pack, B, k, *pack.tables(cap, x.device))
+    y = torch.empty(B * k, pack.dim, dtype=out_dtype, device=x.device)
+    nbytes = lib().tribe_encoder_extend_workspace_bytes(C.byref(d), cap)
+    ws = workspace(nbytes, x.device)
+    check(lib().tribe_encoder_extend_fwd(C.byref(d), x.data_ptr(), y.data_ptr(), _DT[out_dtype], k_cache.data_ptr(), v_cache.data_ptr(), cap, pos,
+                                         ws.data_ptr(), ws.numel(), _stream()), what)
+    return y
+
+
 # --------------------------------------------------------------------------------------
 # voxel head, pool, losses
 # --------------------------------------------------------------------------------------

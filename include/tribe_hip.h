@@ -342,6 +342,32 @@ int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, void* y, int32
 int tribe_encoder_prefill_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
                               int64_t cap, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- block append: k positions at once onto a cache that holds `pos` of them (k >= 1, pos >= 0, pos + k <= cap; pos = 0 is a prefill) ----
+ * Rows of a block are ordered [B, k]: row b * k + t is step t of sequence b, at position pos + t.
+ *
+ * tribe_kv_append_block: tribe_kv_append for k rows per sequence.  qkv: fused bf16 [B * k, 3 * heads * dim_head].  Rotates the q heads and
+ *   the k heads of row b * k + t in place at position pos + t (cos / sin f32 [>= pos + k, rot_dim / 2]; tribe_rotary_fwd's arithmetic, bit
+ *   for bit) and stores the rotated k heads and the v heads into slot pos + t.  One launch; no other slot is touched.
+ * tribe_attention_extend_fwd: rectangular causal attention against the cache (the 16-query-rows-per-wave flash kernel of
+ *   csrc/attention.hip in its block-append form).  Query row b * k + t (head h at q + row * ld_q + h * dim_head; ld_q = 3 * inner reads the
+ *   q heads of the block's fused rows, already rotated) sees keys j <= pos + t of K, V [B, heads, cap, dim_head], which must already hold
+ *   slots 0 .. pos + k - 1 (tribe_kv_append_block first).  out: bf16 [B * k, heads * dim_head].  dim_head in {64, 128, 192, 384}.  Nothing
+ *   at or beyond slot pos + k is read.  B * heads * ceil(k / 128) workgroups, each walking its keys serially: no workspace, the same call
+ *   gives the same bits.
+ * tribe_encoder_extend_fwd: the causal encoder at positions pos .. pos + k - 1 given the caches of positions 0 .. pos - 1; d->T = k,
+ *   x f32 [B * k, dim] (updated in place), y [B * k, dim]; d->cos_tab / sin_tab hold at least pos + k rows.  Per layer what
+ *   tribe_encoder_step_fwd does, for k rows per sequence: ScaleNorm, QKV GEMM, tribe_kv_append_block, tribe_attention_extend_fwd,
+ *   out-proj + residual, ScaleNorm, FF1 + GELU, FF2 + residual; then the final ScaleNorm. */
+int tribe_kv_append_block(uint16_t* qkv, int64_t B, int64_t k, int32_t heads, int32_t dim_head, int32_t rot_dim, int32_t interleaved,
+                          const float* cos_tab, const float* sin_tab, int64_t pos, uint16_t* k_cache, uint16_t* v_cache, int64_t cap,
+                          void* stream);
+int tribe_attention_extend_fwd(const uint16_t* q, int64_t ld_q, const uint16_t* k_cache, const uint16_t* v_cache, int64_t B,
+                               int32_t heads, int32_t dim_head, int64_t cap, int64_t pos, int64_t k, float scale, uint16_t* out,
+                               void* stream);
+size_t tribe_encoder_extend_workspace_bytes(const tribe_encoder_desc* d, int64_t cap);
+int tribe_encoder_extend_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+                             int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * a16-a18: building blocks of the frozen extractors (HF transformers architectures)
  * ------------------------------------------------------------------------- */
