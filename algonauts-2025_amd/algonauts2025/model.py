@@ -207,11 +207,12 @@ class FmriEncoder(nn.Module):
             drop = list(np.random.choice(drop, len(drop) - 1, replace=False))
         return drop
 
-    def _fused_embed(self, data: dict[str, torch.Tensor], add_embeddings: bool, pos0: int = 0, draw: bool = True
+    def _fused_embed(self, data: dict[str, torch.Tensor], add_embeddings: bool, pos0: int = 0, draw: bool = True, time_pos: bool = True
                      ) -> tuple[torch.Tensor, int, int]:
         """aggregate_features (+ transformer_forward's embedding adds when `add_embeddings`): f32 [B*T, hidden].
         pos0: the position of the first time step (a stream's steps: rows pos0 .. pos0 + T - 1 of time_pos_embed); draw=False: no
-        modality-dropout draw (streaming is eval-only and leaves the RNG alone)."""
+        modality-dropout draw (streaming is eval-only and leaves the RNG alone); time_pos=False: the subject embedding only -- the caller
+        adds the positional rows itself (SlotStream: one row index per sample)."""
         for modality in data.keys():
             if modality in self.feature_dims:
                 break
@@ -224,10 +225,10 @@ class FmriEncoder(nn.Module):
             # reference behaviour: a 3072//n zero block cannot be summed with hidden-wide projections (model.py:143-144,163-164)
             raise RuntimeError(f"The size of tensor a ({self.hidden}) must match the size of tensor b ({self.hidden // n_mod}) "
                                "at non-singleton dimension 2")
-        if add_embeddings and pos0 + T > self.time_pos_embed.shape[1]:
+        if add_embeddings and time_pos and pos0 + T > self.time_pos_embed.shape[1]:
             raise RuntimeError(f"sequence length {pos0 + T} exceeds the positional table ({self.time_pos_embed.shape[1]})")
         dropped = self._draw_modality_dropout() if draw else []
-        pos = f32c(self.time_pos_embed)[0][pos0:] if add_embeddings else None
+        pos = f32c(self.time_pos_embed)[0][pos0:] if add_embeddings and time_pos else None
         semb, sid = None, None
         if add_embeddings and hasattr(self, "subject_embed"):
             semb = f32c(self.subject_embed.weight)
@@ -413,12 +414,15 @@ class FmriEncoder(nn.Module):
         return out
 
     # --- streaming (causal encoders): one stimulus step at a time ------------------------------------
-    def stream(self, batch_size: int, max_len: int | None = None) -> "EncoderStream":
+    def stream(self, batch_size: int, max_len: int | None = None, independent: bool = False) -> "EncoderStream | SlotStream":
         """A stream of `batch_size` timelines of up to `max_len` stimulus steps (None: config.max_timesteps) through this model:
-        EncoderStream.push(one step) -> the prediction at that step.  Needs `causal=True`."""
+        EncoderStream.push(one step) -> the prediction at that step.  Needs `causal=True`.  independent=True: a SlotStream, whose
+        timelines start, advance and end independently of each other (one position per slot)."""
         max_len = self.config.max_timesteps if max_len is None else max_len
         if max_len > self.time_pos_embed.shape[1]:
             raise ValueError(f"FmriEncoder.stream: max_len={max_len} exceeds the positional table ({self.time_pos_embed.shape[1]} steps)")
+        if independent:
+            return SlotStream(self, batch_size, max_len)
         return EncoderStream(self, batch_size, max_len)
 
     # --- contrastive alignment helpers (model.py:177-241) -----------------------------------------
@@ -577,3 +581,87 @@ class EncoderStream:
         model.encoder._check_stream("prefill", x.view(B, T, -1), self.cache, T)
         y = model.encoder.prefill_tokens(x, B, T, self.cache, torch.bfloat16)
         return model.predictor.forward_tokens(y.view(B, T, -1), data["subject_id"])
+
+
+class SlotStream:
+    """Independent timelines through one causal FmriEncoder (FmriEncoder.stream(..., independent=True)): every one of the B slots has its own
+    position, a call advances any subset of them, and a finished slot is reset and refilled while the others carry on -- at the cost of one
+    step at batch size B per call (HipEncoder.step_slots / extend_slots on an EncoderSlots), where B separate streams pay every launch B
+    times.  Each slot's positional row is its own: time_pos_embed[0, positions[b] + t].
+
+    Outputs as EncoderStream's (the un-pooled stimulus grid; inference only); the rows of inactive slots are zeros.  `subject_id` and
+    every modality are given for all B slots in every call; what an inactive slot holds is not read into any result."""
+
+    def __init__(self, model: FmriEncoder, batch_size: int, max_len: int):
+        self.model = model
+        self.slots = model.encoder.new_slots(batch_size, max_len, model.time_pos_embed.device)
+
+    @property
+    def positions(self) -> list[int]:
+        return list(self.slots.positions)
+
+    def reset(self, slots: tp.Sequence[int] | None = None) -> None:
+        self.slots.reset(slots)
+
+    def _steps(self, what: str, data: dict[str, torch.Tensor], one: bool, active) -> tuple[int, list[bool]]:
+        """Validates a push batch before anything is launched; returns its number of time steps and one flag per slot."""
+        B, T = self.slots.batch_size, None
+        for modality in self.model.feature_dims:
+            feat = data.get(modality) if modality in self.model.projectors else None
+            if feat is None:
+                continue
+            if feat.ndim not in (3, 4):
+                raise ValueError(f"SlotStream.{what}: {modality}: expected [B, L, D, T] or [B, D, T] features, got {tuple(feat.shape)}")
+            if feat.shape[0] != B:
+                raise ValueError(f"SlotStream.{what}: {modality}: batch size {feat.shape[0]} does not match the stream's {B} slots")
+            if feat.device != self.slots.device:
+                raise ValueError(f"SlotStream.{what}: {modality} is on {feat.device}, the stream on {self.slots.device}")
+            if T is not None and feat.shape[-1] != T:
+                raise ValueError(f"SlotStream.{what}: modalities disagree on the number of time steps ({T} vs {feat.shape[-1]})")
+            T = feat.shape[-1]
+        if T is None:
+            raise ValueError(f"SlotStream.{what}: the batch holds none of the modalities {list(self.model.projectors)}")
+        if one and T != 1:
+            raise ValueError(f"SlotStream.{what}: expected one time step per call ([B, L, D, 1] or [B, D, 1]), got {T}")
+        return T, self.model.encoder._select_slots(f"SlotStream.{what}", self.slots, T, active, filled="steps seen")
+
+    def _embed(self, data: dict[str, torch.Tensor], k: int, flags: list[bool]) -> tuple[torch.Tensor, torch.Tensor | None]:
+        """f32 [B*k, hidden] encoder input: projectors + subject embedding as in EncoderStream, plus row positions[b] + t of time_pos_embed
+        for sample b (gathered: one index_select and an add); the rows of inactive slots are zeros.  Also the bool [B, 1] slot mask (None:
+        all active).  Index and mask reach the device through pinned memory on the current stream: no synchronisation."""
+        model, device = self.model, self.slots.device
+        x, B, _ = model._fused_embed(data, add_embeddings=True, draw=False, time_pos=False)
+        rows = [(p if on else 0) + t for p, on in zip(self.slots.positions, flags) for t in range(k)]
+        index = torch.tensor(rows, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+        x += f32c(model.time_pos_embed)[0].index_select(0, index)[:, : x.shape[1]]
+        mask = model.encoder._slot_mask(flags, device)
+        if mask is not None:
+            x = torch.where(mask.repeat_interleave(k, 0), x, 0.0)
+        return x, mask
+
+    @torch.no_grad()
+    def push(self, data: SegmentData | dict, active: tp.Sequence[int] | tp.Sequence[bool] | None = None) -> torch.Tensor:
+        """One stimulus step of every active slot (`active`: None = all, slot indices, or a bool sequence of length B): each modality
+        [B, L, D, 1] or [B, D, 1], plus `subject_id` -> f32 [B, n_outputs], the prediction of slot b at its own step positions[b] given the
+        steps pushed into that slot since its last reset.  Rows of inactive slots are zeros."""
+        model = self.model
+        data = model._batch_dict(data)
+        _, flags = self._steps("push", data, True, active)
+        x, mask = self._embed(data, 1, flags)   # [B, hidden] on the slots' device by construction (_steps)
+        y = model.encoder.step_slots_tokens(x, self.slots, flags, torch.bfloat16)
+        out = model.predictor.forward_tokens(y.view(len(flags), 1, -1), data["subject_id"])[:, :, 0]
+        return out if mask is None else torch.where(mask, out, 0.0)
+
+    @torch.no_grad()
+    def push_block(self, data: SegmentData | dict, active: tp.Sequence[int] | tp.Sequence[bool] | None = None) -> torch.Tensor:
+        """The next k stimulus steps of every active slot at once: each modality [B, L, D, k] or [B, D, k], plus `subject_id` -> f32
+        [B, n_outputs, k], the predictions of slot b at its steps positions[b] .. positions[b]+k-1.  k is the same for all slots of a
+        call.  Rows of inactive slots are zeros."""
+        model = self.model
+        data = model._batch_dict(data)
+        k, flags = self._steps("push_block", data, False, active)
+        B = len(flags)
+        x, mask = self._embed(data, k, flags)
+        y = model.encoder.extend_slots_tokens(x, B, k, self.slots, flags, torch.bfloat16)
+        out = model.predictor.forward_tokens(y.view(B, k, -1), data["subject_id"])
+        return out if mask is None else torch.where(mask.view(B, 1, 1), out, 0.0)

@@ -66,6 +66,9 @@ __device__ __forceinline__ int swz_chunk(int chunk, int row) {
 // K / V rows come from a.k / a.v + b * kv_stride_b + hk * kv_stride_h, ld_kv apart, through the same staging.  Every place the mask lives
 // takes the query's POSITION (qp0 = pos + q0) where the square form takes its row, and the key count Tk where it takes T; with EXTEND = 0
 // pos is the constant 0 and Tk is T, so the square instantiations compile to what they were.  No cache slot at or beyond Tk is read.
+// EXTEND = 2: the slot form (tribe_attention_extend_slots_fwd) -- the same kernel with pos read once per workgroup from a.pos_slots[b], so
+// every sequence of the cache sits at a position of its own and a workgroup's result depends on its own sequence only; a sequence whose
+// value lies outside [0, cap - T] takes no part and its rows are written as zeros.  EXTEND = 0 and 1 never read the two added fields.
 template <int DH, int CAUSAL, int RELKEY, int EXTEND = 0>
 __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
   using C = AttnCfg<DH>;
@@ -76,8 +79,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
 
   static_assert(!EXTEND || (CAUSAL && !RELKEY), "the block-append form is causal and has no relative_key bias");
   const int T = a.T;                          // query rows per (sequence, head)
-  const int pos = EXTEND ? a.pos : 0;         // position of query row 0
-  const int Tk = EXTEND ? a.pos + a.T : T;    // keys
+  int pos = EXTEND ? a.pos : 0;               // position of query row 0 (EXTEND = 2: read per sequence below; a.pos is unused)
+  int Tk = EXTEND ? a.pos + a.T : T;          // keys
   const float scale_log2e = a.scale_log2e;
   // Workgroups are dealt to the 8 XCDs round-robin by id, and each XCD has its own L2.  All query blocks of one (sequence,
   // head) pair read the same K / V (1.5 MiB at T = 1024, DH = 384): keep them on ONE XCD -- id % 8 picks the XCD, the ids that
@@ -90,6 +93,19 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_kernel(const AttnArgs a) {
   const int h = pair % a.heads_q;
   const int b = pair / a.heads_q;
   const int hk = h / a.group;
+  if (EXTEND == 2) {
+    pos = a.pos_slots[b];                     // workgroup-uniform
+    if (pos < 0 || pos > a.cap - T) {         // takes no part (or out of range, treated the same): zero rows, no cache slot is read
+      const int q = qb * 128 + wave * 16 + l15;
+      if (q < T) {
+        unsigned short* orow = a.out + ((int64_t)b * T + q) * a.ld_out + (int64_t)h * DH + 4 * fq;
+#pragma unroll
+        for (int dt = 0; dt < C::DT; ++dt) *(u16x4_t*)(orow + 16 * dt) = u16x4_t{0, 0, 0, 0};
+      }
+      return;
+    }
+    Tk = pos + T;
+  }
   const int64_t ld = a.ld_kv;
   const unsigned short* qbase = a.q + (int64_t)b * T * a.ld_q + (int64_t)h * DH;
   const unsigned short* kbase = EXTEND ? a.k + (int64_t)b * a.kv_stride_b + (int64_t)hk * a.kv_stride_h : a.k + (int64_t)b * T * ld + (int64_t)hk * DH;
@@ -961,7 +977,52 @@ int launch_attn_extend(const AttnArgs& a, int64_t B, hipStream_t s) {
   return 0;
 }
 
+// the slot form: the block-append grid, the position per sequence (a.pos_slots)
+template <int DH>
+int launch_attn_extend_slots(const AttnArgs& a, int64_t B, hipStream_t s) {
+  using C = AttnCfg<DH>;
+  raise_dynamic_lds_once<attn_fwd_kernel<DH, 1, 0, 2>>(C::SMEM);
+  const int64_t nblocks = (B * a.heads_q + 7) / 8 * 8 * a.qblocks;
+  if (nblocks >= (1ll << 31)) { tribe_set_error("tribe_attention_extend_slots_fwd: grid too large"); return -1; }
+  hipLaunchKernelGGL((attn_fwd_kernel<DH, 1, 0, 2>), dim3((unsigned)nblocks), dim3(512), C::SMEM, s, a);
+  TRIBE_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int tribe_attention_extend_slots_fwd(const uint16_t* q, int64_t ld_q, const uint16_t* k_cache, const uint16_t* v_cache, int64_t B,
+                                                int32_t heads, int32_t dim_head, int64_t cap, const int32_t* pos, int64_t k, float scale,
+                                                uint16_t* out, void* stream) {
+  TRIBE_REQUIRE(q && k_cache && v_cache && out && pos, "tribe_attention_extend_slots_fwd: null pointer");
+  TRIBE_REQUIRE(B > 0 && heads > 0, "tribe_attention_extend_slots_fwd: bad shape (B=%lld, heads=%d)", (long long)B, heads);
+  TRIBE_REQUIRE(dim_head == 64 || dim_head == 128 || dim_head == 192 || dim_head == 384,
+                "tribe_attention_extend_slots_fwd: dim_head=%d not in {64,128,192,384}", dim_head);
+  TRIBE_REQUIRE(k >= 1 && cap < (1ll << 31) && k <= cap,
+                "tribe_attention_extend_slots_fwd: k=%lld positions per sequence do not fit the cache capacity %lld (1 <= k <= cap < 2^31)",
+                (long long)k, (long long)cap);
+  TRIBE_REQUIRE(ld_q >= (int64_t)heads * dim_head && ld_q % 8 == 0,
+                "tribe_attention_extend_slots_fwd: ld_q=%lld must cover heads * dim_head and be a multiple of 8", (long long)ld_q);
+  TRIBE_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0 && ((uintptr_t)out % 8) == 0 &&
+                    ((uintptr_t)pos % 4) == 0,
+                "tribe_attention_extend_slots_fwd: q and the caches must be 16-byte aligned, out 8-byte aligned, pos 4-byte aligned");
+  TRIBE_REQUIRE(B * heads < (1ll << 31), "tribe_attention_extend_slots_fwd: B * heads too large");
+  AttnArgs a{};
+  a.q = q; a.k = k_cache; a.v = v_cache; a.out = out;
+  a.ld_q = ld_q; a.ld_kv = dim_head; a.ld_out = (int64_t)heads * dim_head;
+  a.kv_stride_b = (int64_t)heads * cap * dim_head; a.kv_stride_h = cap * dim_head;
+  a.T = (int)k; a.cap = (int)cap; a.pos_slots = pos; a.heads_q = heads; a.group = 1;
+  a.scale_log2e = scale * 1.4426950408889634f;
+  a.qblocks = (int)((k + 127) / 128);
+  a.n_bh = (int)(B * heads);
+  hipStream_t s = (hipStream_t)stream;
+  switch (dim_head) {
+    case 64: return launch_attn_extend_slots<64>(a, B, s);
+    case 128: return launch_attn_extend_slots<128>(a, B, s);
+    case 192: return launch_attn_extend_slots<192>(a, B, s);
+    default: return launch_attn_extend_slots<384>(a, B, s);
+  }
+}
 
 extern "C" int tribe_attention_extend_fwd(const uint16_t* q, int64_t ld_q, const uint16_t* k_cache, const uint16_t* v_cache, int64_t B,
                                           int32_t heads, int32_t dim_head, int64_t cap, int64_t pos, int64_t k, float scale, uint16_t* out,

@@ -49,6 +49,9 @@ struct AttnArgs {
   // 0 .. pos + T - 1 of a KV cache -- K / V of (b, hk) start at k + b * kv_stride_b + hk * kv_stride_h (elements), rows ld_kv apart
   int64_t kv_stride_b, kv_stride_h;
   int pos;
+  // slot form (attn_fwd_kernel<.., EXTEND = 2>): sequence b's position is pos_slots[b] (device); one outside [0, cap - T] takes no part
+  int cap;
+  const int32_t* pos_slots;
 };
 
 // compile-time loop: the accumulator tile index selects literal registers (attn_acc_regs.h)

@@ -22,6 +22,7 @@
 // never loaded.
 #include "host_plan.h"
 #include "rotary_pairs.h"
+#include <type_traits>
 
 namespace {
 
@@ -29,10 +30,15 @@ constexpr float DECODE_M_EMPTY = -1.0e30f;   // running maximum of a part that h
 constexpr int DECODE_MAX_SPLITS = 32;
 constexpr int DECODE_MIN_KEYS = 64;          // keys per split at least: one pass of the four waves at U = 2
 
+// Pos = int64_t: every sequence starts at position pos0 (tribe_kv_append, tribe_kv_append_block).  Pos = const int32_t*: the slot form
+// (tribe_kv_append_slots) -- sequence b starts at pos0[b], and one whose value lies outside [0, cap - T] takes no part: neither its cache
+// run nor its qkv rows are touched.  The argument has the same size either way, so the int64_t form is the kernel it was.
+template <class Pos>
 __global__ __launch_bounds__(256) void kv_append_kernel(unsigned short* __restrict__ qkv, int64_t B, int64_t T, int heads, int dim_head,
                                                         int rot_dim, int interleaved, const float* __restrict__ cos_tab,
-                                                        const float* __restrict__ sin_tab, int64_t pos0, unsigned short* __restrict__ kc,
+                                                        const float* __restrict__ sin_tab, Pos pos0, unsigned short* __restrict__ kc,
                                                         unsigned short* __restrict__ vc, int64_t cap) {
+  constexpr bool SLOTS = std::is_pointer<Pos>::value;
   const int half = rot_dim >> 1;
   const int items_per_head = dim_head >> 3;   // 8 elements each
   const int rot_items = rot_dim >> 3;
@@ -43,7 +49,15 @@ __global__ __launch_bounds__(256) void kv_append_kernel(unsigned short* __restri
     const int it = (int)(t % items_per_head); t /= items_per_head;
     const int hh = (int)(t % (3 * heads));
     const int64_t row = t / (3 * heads);                // b * T + step
-    const int64_t b = row / T, pos = pos0 + (row - b * T);
+    const int64_t b = row / T;
+    int64_t first;
+    if constexpr (SLOTS) {
+      first = pos0[b];
+      if (first < 0 || first > cap - T) continue;   // takes no part, or out of range: treated the same
+    } else {
+      first = pos0;
+    }
+    const int64_t pos = first + (row - b * T);
     const int sec = hh / heads, h = hh - sec * heads;   // 0 q, 1 k, 2 v
     unsigned short* base = qkv + row * 3 * inner + (int64_t)hh * dim_head;
     unsigned short* slot = (sec == 1 ? kc : vc) + ((b * heads + h) * cap + pos) * dim_head;
@@ -89,8 +103,10 @@ __global__ __launch_bounds__(256) void kv_fill_kernel(const unsigned short* __re
   }
 }
 
-// merge of (m, l, o) parts in index order; `get(i, &m, &l, &o)` reads part i
-template <class Get>
+// merge of (m, l, o) parts in index order; `get(i, &m, &l, &o)` reads part i.  The compiler contracts `L += l * w` into a fused
+// multiply-add in the uniform kernels; FUSED states that arithmetic outright for the slot forms, where it would otherwise leave some of
+// the products unfused (seen at dim_head 384) and the two forms would round differently.
+template <bool FUSED = false, class Get>
 __device__ __forceinline__ void merge_parts(int n_parts, Get get, float* M_out, float* L_out, float* O_out) {
   float M = DECODE_M_EMPTY;
   for (int i = 0; i < n_parts; ++i) { float m, l, o; get(i, &m, &l, &o); M = fmaxf(M, m); }
@@ -99,20 +115,29 @@ __device__ __forceinline__ void merge_parts(int n_parts, Get get, float* M_out, 
     float m, l, o;
     get(i, &m, &l, &o);
     const float w = exp2f(m - M);
-    L += l * w;
-    O += o * w;
+    if (FUSED) {
+      L = fmaf(l, w, L);
+      O = fmaf(o, w, O);
+    } else {
+      L += l * w;
+      O += o * w;
+    }
   }
   *M_out = M; *L_out = L; *O_out = O;
 }
 
 // grid (splits, heads, B); split s owns keys [s * chunk, min(n, (s + 1) * chunk)).  splits == 1: writes `out`; else part (m, l) to ws_ml
 // and o to ws_o, part index (b * heads + h) * splits + s.
-template <int DH>
+// SLOTS: a key count per sequence (tribe_attention_decode_slots_fwd).  n is the host's upper bound n_max; sequence b holds
+// n_b = min(pos_slots[b] + 1, n) keys, or none when pos_slots[b] lies outside [0, cap - 1] (inactive).  A split whose range starts at or
+// beyond n_b loads nothing and hands on the empty part (DECODE_M_EMPTY, 0, 0); a row whose parts are all empty is written as +0.
+template <int DH, int SLOTS>
 __global__ __launch_bounds__(256) void attn_decode_split_kernel(const unsigned short* __restrict__ q, int64_t ld_q,
                                                                 const unsigned short* __restrict__ kc,
                                                                 const unsigned short* __restrict__ vc, int heads, int64_t cap, int64_t n,
                                                                 int64_t chunk, int splits, float scale_log2e, float* __restrict__ ws_ml,
-                                                                float* __restrict__ ws_o, unsigned short* __restrict__ out) {
+                                                                float* __restrict__ ws_o, unsigned short* __restrict__ out,
+                                                                const int32_t* __restrict__ pos_slots) {
   constexpr int CH = DH / 64;            // 16-byte pieces per lane and key
   constexpr int U = CH <= 2 ? 4 : 2;     // keys per group in flight
   __shared__ float sh_ml[4][2];
@@ -120,7 +145,12 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const unsigned s
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 3, j = lane & 7;
   const int s = blockIdx.x, h = blockIdx.y;
   const int64_t b = blockIdx.z;
-  const int64_t k0 = (int64_t)s * chunk, k1 = (k0 + chunk < n) ? k0 + chunk : n;
+  int64_t nb = n;
+  if (SLOTS) {
+    const int64_t p = pos_slots[b];
+    nb = (p < 0 || p >= cap) ? 0 : (p + 1 < n ? p + 1 : n);
+  }
+  const int64_t k0 = (int64_t)s * chunk, k1 = (k0 + chunk < nb) ? k0 + chunk : nb;
   const unsigned short* qrow = q + b * ld_q + (int64_t)h * DH;
   const unsigned short* krun = kc + (b * heads + h) * cap * DH;
   const unsigned short* vrun = vc + (b * heads + h) * cap * DH;
@@ -219,8 +249,10 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const unsigned s
   const int64_t part = (b * heads + h) * splits + s;
   for (int t = tid; t < DH; t += 256) {
     float Mw, Lw, Ow;
-    merge_parts(4, [&](int i, float* pm, float* pl, float* po) { *pm = sh_ml[i][0]; *pl = sh_ml[i][1]; *po = sh_o[i][t]; }, &Mw, &Lw, &Ow);
+    merge_parts<SLOTS != 0>(4, [&](int i, float* pm, float* pl, float* po) { *pm = sh_ml[i][0]; *pl = sh_ml[i][1]; *po = sh_o[i][t]; }, &Mw, &Lw,
+                            &Ow);
     if (splits == 1) {
+      if (SLOTS && !(Lw > 0.f)) Lw = 1.f;   // no key (Ow is 0): +0, not 0 / 0
       out[(b * heads + h) * DH + t] = f32_to_bf16(Ow / Lw);
     } else {
       ws_o[part * DH + t] = Ow;
@@ -229,7 +261,8 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const unsigned s
   }
 }
 
-// grid (heads, B): the parts of one (b, h), in split order
+// grid (heads, B): the parts of one (b, h), in split order.  SLOTS: a row without a key (every part empty, L = 0) is written as +0.
+template <int SLOTS>
 __global__ __launch_bounds__(256) void attn_decode_combine_kernel(const float* __restrict__ ws_ml, const float* __restrict__ ws_o, int heads,
                                                                   int dim_head, int splits, unsigned short* __restrict__ out) {
   const int64_t bh = (int64_t)blockIdx.y * heads + blockIdx.x;
@@ -237,8 +270,9 @@ __global__ __launch_bounds__(256) void attn_decode_combine_kernel(const float* _
   const float* o = ws_o + bh * splits * dim_head;
   for (int t = threadIdx.x; t < dim_head; t += 256) {
     float M, L, O;
-    merge_parts(splits, [&](int i, float* pm, float* pl, float* po) { *pm = ml[i * 2]; *pl = ml[i * 2 + 1]; *po = o[(int64_t)i * dim_head + t]; },
+    merge_parts<SLOTS != 0>(splits, [&](int i, float* pm, float* pl, float* po) { *pm = ml[i * 2]; *pl = ml[i * 2 + 1]; *po = o[(int64_t)i * dim_head + t]; },
                 &M, &L, &O);
+    if (SLOTS && !(L > 0.f)) L = 1.f;   // no key in any part (O is 0): +0, not 0 / 0
     out[bh * dim_head + t] = f32_to_bf16(O / L);
   }
 }
@@ -284,7 +318,7 @@ extern "C" int tribe_kv_append(uint16_t* qkv, int64_t B, int32_t heads, int32_t 
                     ((uintptr_t)cos_tab % 16) == 0 && ((uintptr_t)sin_tab % 16) == 0,
                 "tribe_kv_append: buffers must be 16-byte aligned");
   const int64_t total = B * 3 * heads * (dim_head / 8);
-  hipLaunchKernelGGL(kv_append_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, qkv, B, (int64_t)1, heads, dim_head,
+  hipLaunchKernelGGL(kv_append_kernel<int64_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, qkv, B, (int64_t)1, heads, dim_head,
                      rot_dim, interleaved, cos_tab, sin_tab, pos, k_cache, v_cache, cap);
   TRIBE_LAUNCH_CHECK();
   return 0;
@@ -307,7 +341,7 @@ extern "C" int tribe_kv_append_block(uint16_t* qkv, int64_t B, int64_t k, int32_
                     ((uintptr_t)cos_tab % 16) == 0 && ((uintptr_t)sin_tab % 16) == 0,
                 "tribe_kv_append_block: buffers must be 16-byte aligned");
   const int64_t total = B * k * 3 * heads * (dim_head / 8);
-  hipLaunchKernelGGL(kv_append_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, qkv, B, k, heads, dim_head, rot_dim,
+  hipLaunchKernelGGL(kv_append_kernel<int64_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, qkv, B, k, heads, dim_head, rot_dim,
                      interleaved, cos_tab, sin_tab, pos, k_cache, v_cache, cap);
   TRIBE_LAUNCH_CHECK();
   return 0;
@@ -349,8 +383,8 @@ extern "C" int tribe_attention_decode_fwd(const uint16_t* q, int64_t ld_q, const
   const dim3 grid((unsigned)sp, (unsigned)heads, (unsigned)B);
   hipStream_t s = (hipStream_t)stream;
 #define TRIBE_DECODE_LAUNCH(DH)                                                                                                        \
-  hipLaunchKernelGGL((attn_decode_split_kernel<DH>), grid, dim3(256), 0, s, q, ld_q, k_cache, v_cache, heads, cap, n, chunk, sp, \
-                     scale_log2e, ws_ml, ws_o, out)
+  hipLaunchKernelGGL((attn_decode_split_kernel<DH, 0>), grid, dim3(256), 0, s, q, ld_q, k_cache, v_cache, heads, cap, n, chunk, sp, \
+                     scale_log2e, ws_ml, ws_o, out, (const int32_t*)nullptr)
   switch (dim_head) {
     case 64: TRIBE_DECODE_LAUNCH(64); break;
     case 128: TRIBE_DECODE_LAUNCH(128); break;
@@ -360,7 +394,77 @@ extern "C" int tribe_attention_decode_fwd(const uint16_t* q, int64_t ld_q, const
 #undef TRIBE_DECODE_LAUNCH
   TRIBE_LAUNCH_CHECK();
   if (sp > 1) {
-    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3((unsigned)heads, (unsigned)B), dim3(256), 0, s, ws_ml, ws_o, heads, dim_head, sp, out);
+    hipLaunchKernelGGL(attn_decode_combine_kernel<0>, dim3((unsigned)heads, (unsigned)B), dim3(256), 0, s, ws_ml, ws_o, heads, dim_head, sp, out);
+    TRIBE_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---- slots: every sequence of the cache at a position of its own (pos: device int32 [B]; -1, or any value out of range, = takes no part) ----
+extern "C" int tribe_kv_append_slots(uint16_t* qkv, int64_t B, int64_t k, int32_t heads, int32_t dim_head, int32_t rot_dim,
+                                     int32_t interleaved, const float* cos_tab, const float* sin_tab, const int32_t* pos, uint16_t* k_cache,
+                                     uint16_t* v_cache, int64_t cap, void* stream) {
+  TRIBE_REQUIRE(qkv && k_cache && v_cache && pos, "tribe_kv_append_slots: null pointer");
+  TRIBE_REQUIRE(B > 0 && heads > 0 && dim_head > 0 && dim_head % 8 == 0,
+                "tribe_kv_append_slots: bad shape (B=%lld, heads=%d, dim_head=%d; dim_head %% 8 == 0)", (long long)B, heads, dim_head);
+  TRIBE_REQUIRE(k >= 1 && k <= cap && cap < (1ll << 31),
+                "tribe_kv_append_slots: k=%lld positions per sequence do not fit the cache capacity %lld (1 <= k <= cap < 2^31)", (long long)k,
+                (long long)cap);
+  TRIBE_REQUIRE(rot_dim >= 0 && rot_dim <= dim_head && rot_dim % 8 == 0,
+                "tribe_kv_append_slots: rot_dim=%d must be a multiple of 8 and <= dim_head=%d", rot_dim, dim_head);
+  TRIBE_REQUIRE(rot_dim == 0 || (cos_tab && sin_tab), "tribe_kv_append_slots: rotary tables missing");
+  TRIBE_REQUIRE(interleaved == 0 || interleaved == 1, "tribe_kv_append_slots: interleaved must be 0 or 1");
+  TRIBE_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0 &&
+                    ((uintptr_t)cos_tab % 16) == 0 && ((uintptr_t)sin_tab % 16) == 0 && ((uintptr_t)pos % 4) == 0,
+                "tribe_kv_append_slots: buffers must be 16-byte aligned, pos 4-byte aligned");
+  const int64_t total = B * k * 3 * heads * (dim_head / 8);
+  hipLaunchKernelGGL(kv_append_kernel<const int32_t*>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, qkv, B, k, heads, dim_head,
+                     rot_dim, interleaved, cos_tab, sin_tab, pos, k_cache, v_cache, cap);
+  TRIBE_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int tribe_attention_decode_slots_fwd(const uint16_t* q, int64_t ld_q, const uint16_t* k_cache, const uint16_t* v_cache, int64_t B,
+                                                int32_t heads, int32_t dim_head, int64_t cap, const int32_t* pos, int64_t n_max, float scale,
+                                                uint16_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(q && k_cache && v_cache && out && pos, "tribe_attention_decode_slots_fwd: null pointer");
+  TRIBE_REQUIRE(B > 0 && B < 65536 && heads > 0 && heads < 65536, "tribe_attention_decode_slots_fwd: bad shape (B=%lld, heads=%d)", (long long)B,
+                heads);
+  TRIBE_REQUIRE(decode_dim_head_ok(dim_head), "tribe_attention_decode_slots_fwd: dim_head=%d must be 64, 128, 192 or 384", dim_head);
+  TRIBE_REQUIRE(n_max >= 1 && n_max <= cap && cap < (1ll << 31), "tribe_attention_decode_slots_fwd: n_max=%lld keys outside 1 .. capacity %lld",
+                (long long)n_max, (long long)cap);
+  TRIBE_REQUIRE(ld_q >= (int64_t)heads * dim_head && ld_q % 8 == 0,
+                "tribe_attention_decode_slots_fwd: ld_q=%lld must cover heads * dim_head and be a multiple of 8", (long long)ld_q);
+  TRIBE_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0 && ((uintptr_t)pos % 4) == 0,
+                "tribe_attention_decode_slots_fwd: q and the caches must be 16-byte aligned, pos 4-byte aligned");
+  // the split count and the chunk of tribe_attention_decode_fwd at n = n_max: with every pos[b] + 1 == n_max the two calls give the same bits
+  const int sp = decode_splits(B, heads, n_max);
+  float *ws_ml = nullptr, *ws_o = nullptr;
+  if (sp > 1) {
+    TRIBE_REQUIRE(workspace && ((uintptr_t)workspace % 256) == 0,
+                  "tribe_attention_decode_slots_fwd: workspace must be non-null and 256-byte aligned");
+    Arena ws(workspace);
+    ws_ml = ws.take<float>((size_t)B * heads * sp * 2 * sizeof(float));
+    ws_o = ws.take<float>((size_t)B * heads * sp * dim_head * sizeof(float));
+    TRIBE_REQUIRE(workspace_bytes >= ws.off, "tribe_attention_decode_slots_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+  }
+  const int64_t chunk = round_up((n_max + sp - 1) / sp, 8);
+  const float scale_log2e = scale * 1.4426950408889634f;
+  const dim3 grid((unsigned)sp, (unsigned)heads, (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+#define TRIBE_DECODE_LAUNCH(DH)                                                                                                           \
+  hipLaunchKernelGGL((attn_decode_split_kernel<DH, 1>), grid, dim3(256), 0, s, q, ld_q, k_cache, v_cache, heads, cap, n_max, chunk, sp, \
+                     scale_log2e, ws_ml, ws_o, out, pos)
+  switch (dim_head) {
+    case 64: TRIBE_DECODE_LAUNCH(64); break;
+    case 128: TRIBE_DECODE_LAUNCH(128); break;
+    case 192: TRIBE_DECODE_LAUNCH(192); break;
+    default: TRIBE_DECODE_LAUNCH(384); break;
+  }
+#undef TRIBE_DECODE_LAUNCH
+  TRIBE_LAUNCH_CHECK();
+  if (sp > 1) {
+    hipLaunchKernelGGL(attn_decode_combine_kernel<1>, dim3((unsigned)heads, (unsigned)B), dim3(256), 0, s, ws_ml, ws_o, heads, dim_head, sp, out);
     TRIBE_LAUNCH_CHECK();
   }
   return 0;

@@ -390,18 +390,17 @@ extern "C" size_t tribe_encoder_step_workspace_bytes(const tribe_encoder_desc* d
   return ws.off;
 }
 
-extern "C" int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
-                                      int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream) {
-  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_step_fwd: null descriptor");
-  int rc = enc_validate(d);
-  if (rc) return rc;
-  TRIBE_REQUIRE(x && y && workspace && k_cache && v_cache, "tribe_encoder_step_fwd: null pointer");
-  TRIBE_REQUIRE(d->T == 1, "tribe_encoder_step_fwd: a step is one position per sequence (T=%lld)", (long long)d->T);
-  TRIBE_REQUIRE(cap > 0 && pos >= 0 && pos < cap, "tribe_encoder_step_fwd: pos=%lld outside the cache capacity %lld", (long long)pos, (long long)cap);
-  TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "tribe_encoder_step_fwd: workspace must be 256-byte aligned");
+namespace {
+// The launches of a step, after the entry point's own argument checks (`name`, for the messages).  pos_slots == nullptr: every sequence at
+// `pos` (tribe_encoder_step_fwd); else sequence b at pos_slots[b], n_max an upper bound of every pos_slots[b] + 1
+// (tribe_encoder_step_slots_fwd): the same launches, the two cache-aware ones in their slot forms.
+int step_body(const char* name, const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+              int64_t cap, int64_t pos, const int32_t* pos_slots, int64_t n_max, void* workspace, size_t workspace_bytes, void* stream) {
+  int rc = 0;
+  TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", name);
   Arena ws(workspace);
   const StepLayout p = step_layout(d, cap, ws);
-  TRIBE_REQUIRE(workspace_bytes >= ws.off, "tribe_encoder_step_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+  TRIBE_REQUIRE(workspace_bytes >= ws.off, "%s: workspace too small (%zu < %zu)", name, workspace_bytes, ws.off);
   const int64_t M = d->B, inner = p.inner, dim = d->dim;
   const int64_t per_layer = d->B * inner * cap;
   const float scale = 1.0f / sqrtf((float)d->dim_head);
@@ -409,7 +408,7 @@ extern "C" int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, voi
   for (int l = 0; l < d->depth; ++l) {
     const tribe_encoder_layer& L = d->layers_host[l];
     TRIBE_REQUIRE(L.attn_norm_g && L.w_qkv && L.w_out && L.ff_norm_g && L.w_ff1 && L.b_ff1 && L.w_ff2 && L.b_ff2,
-                  "tribe_encoder_step_fwd: layer %d has a null parameter", l);
+                  "%s: layer %d has a null parameter", name, l);
     rc = tribe_scalenorm_fwd(x, M, dim, L.attn_norm_g, d->norm_gain_scale, d->norm_eps, p.xn, TRIBE_BF16, stream);
     if (rc) return rc;
     tribe_gemm_desc g = Linear(TRIBE_ROLE_QKV, M, p.xn, dim, L.w_qkv, nullptr, p.qkv, 3 * inner, TRIBE_BF16);
@@ -417,10 +416,18 @@ extern "C" int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, voi
     rc = tribe_gemm_bf16(&g, stream);
     if (rc) return rc;
     uint16_t *kc = k_cache + l * per_layer, *vc = v_cache + l * per_layer;
-    rc = tribe_kv_append(p.qkv, d->B, d->heads, d->dim_head, d->rot_dim, d->rotary_interleaved, d->cos_tab, d->sin_tab, pos, kc, vc, cap, stream);
-    if (rc) return rc;
-    rc = tribe_attention_decode_fwd(p.qkv, 3 * inner, kc, vc, d->B, d->heads, d->dim_head, cap, pos + 1, scale, p.ao, p.attn_ws, p.attn_bytes,
-                                    stream);
+    if (pos_slots) {
+      rc = tribe_kv_append_slots(p.qkv, d->B, 1, d->heads, d->dim_head, d->rot_dim, d->rotary_interleaved, d->cos_tab, d->sin_tab, pos_slots, kc,
+                                 vc, cap, stream);
+      if (rc) return rc;
+      rc = tribe_attention_decode_slots_fwd(p.qkv, 3 * inner, kc, vc, d->B, d->heads, d->dim_head, cap, pos_slots, n_max, scale, p.ao, p.attn_ws,
+                                            p.attn_bytes, stream);
+    } else {
+      rc = tribe_kv_append(p.qkv, d->B, d->heads, d->dim_head, d->rot_dim, d->rotary_interleaved, d->cos_tab, d->sin_tab, pos, kc, vc, cap, stream);
+      if (rc) return rc;
+      rc = tribe_attention_decode_fwd(p.qkv, 3 * inner, kc, vc, d->B, d->heads, d->dim_head, cap, pos + 1, scale, p.ao, p.attn_ws, p.attn_bytes,
+                                      stream);
+    }
     if (rc) return rc;
     g = Linear(TRIBE_ROLE_OUT_PROJ, M, p.ao, inner, L.w_out, nullptr, x, dim, TRIBE_F32).residual(x);
     g.res_scale = L.attn_res_scale;
@@ -440,6 +447,32 @@ extern "C" int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, voi
     if (rc) return rc;
   }
   return tribe_scalenorm_fwd(x, M, dim, d->final_norm_g, d->norm_gain_scale, d->norm_eps, y, y_dtype, stream);
+}
+}  // namespace
+
+extern "C" int tribe_encoder_step_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+                                      int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_step_fwd: null descriptor");
+  int rc = enc_validate(d);
+  if (rc) return rc;
+  TRIBE_REQUIRE(x && y && workspace && k_cache && v_cache, "tribe_encoder_step_fwd: null pointer");
+  TRIBE_REQUIRE(d->T == 1, "tribe_encoder_step_fwd: a step is one position per sequence (T=%lld)", (long long)d->T);
+  TRIBE_REQUIRE(cap > 0 && pos >= 0 && pos < cap, "tribe_encoder_step_fwd: pos=%lld outside the cache capacity %lld", (long long)pos, (long long)cap);
+  return step_body("tribe_encoder_step_fwd", d, x, y, y_dtype, k_cache, v_cache, cap, pos, nullptr, 0, workspace, workspace_bytes, stream);
+}
+
+// every sequence at a position of its own: pos int32 [B] on the device (-1 = takes no part), n_max >= every pos[b] + 1
+extern "C" int tribe_encoder_step_slots_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache,
+                                            uint16_t* v_cache, int64_t cap, const int32_t* pos, int64_t n_max, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_step_slots_fwd: null descriptor");
+  int rc = enc_validate(d);
+  if (rc) return rc;
+  TRIBE_REQUIRE(x && y && workspace && k_cache && v_cache && pos, "tribe_encoder_step_slots_fwd: null pointer");
+  TRIBE_REQUIRE(d->T == 1, "tribe_encoder_step_slots_fwd: a step is one position per sequence (T=%lld)", (long long)d->T);
+  TRIBE_REQUIRE(cap > 0 && n_max >= 1 && n_max <= cap, "tribe_encoder_step_slots_fwd: n_max=%lld keys outside 1 .. capacity %lld",
+                (long long)n_max, (long long)cap);
+  return step_body("tribe_encoder_step_slots_fwd", d, x, y, y_dtype, k_cache, v_cache, cap, 0, pos, n_max, workspace, workspace_bytes, stream);
 }
 
 // ---- block append: d->T = k positions per sequence onto caches that hold `pos` (attention.hip: tribe_attention_extend_fwd) ----
@@ -474,22 +507,21 @@ extern "C" size_t tribe_encoder_extend_workspace_bytes(const tribe_encoder_desc*
   return ws.off;
 }
 
-extern "C" int tribe_encoder_extend_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache,
-                                        uint16_t* v_cache, int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream) {
-  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_extend_fwd: null descriptor");
-  TRIBE_REQUIRE(d->T >= 1 && cap > 0 && pos >= 0 && pos + d->T <= cap,
-                "tribe_encoder_extend_fwd: k=%lld positions from pos=%lld outside the cache capacity %lld (k >= 1, pos >= 0, pos + k <= cap)",
-                (long long)d->T, (long long)pos, (long long)cap);
-  TRIBE_REQUIRE(tribe_internal_attention_fused_supported(d->dim_head), "tribe_encoder_extend_fwd: dim_head=%d not in {64,128,192,384}",
-                d->dim_head);
+namespace {
+// The launches of a block append, after the entry point's own range check (`name`, for the messages).  pos_slots == nullptr: every
+// sequence at `pos` (tribe_encoder_extend_fwd); else sequence b at pos_slots[b] (tribe_encoder_extend_slots_fwd): the same launches, the
+// two cache-aware ones in their slot forms.
+int extend_body(const char* name, const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+                int64_t cap, int64_t pos, const int32_t* pos_slots, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(tribe_internal_attention_fused_supported(d->dim_head), "%s: dim_head=%d not in {64,128,192,384}", name, d->dim_head);
   int rc = enc_validate(d);
   if (rc) return rc;
-  TRIBE_REQUIRE(x && y && workspace && k_cache && v_cache, "tribe_encoder_extend_fwd: null pointer");
-  TRIBE_REQUIRE(((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0, "tribe_encoder_extend_fwd: caches must be 16-byte aligned");
-  TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "tribe_encoder_extend_fwd: workspace must be 256-byte aligned");
+  TRIBE_REQUIRE(x && y && workspace && k_cache && v_cache, "%s: null pointer", name);
+  TRIBE_REQUIRE(((uintptr_t)k_cache % 16) == 0 && ((uintptr_t)v_cache % 16) == 0, "%s: caches must be 16-byte aligned", name);
+  TRIBE_REQUIRE(((uintptr_t)workspace % 256) == 0, "%s: workspace must be 256-byte aligned", name);
   Arena ws(workspace);
   const ExtendLayout p = extend_layout(d, ws);
-  TRIBE_REQUIRE(workspace_bytes >= ws.off, "tribe_encoder_extend_fwd: workspace too small (%zu < %zu)", workspace_bytes, ws.off);
+  TRIBE_REQUIRE(workspace_bytes >= ws.off, "%s: workspace too small (%zu < %zu)", name, workspace_bytes, ws.off);
   const int64_t M = p.M, inner = p.inner, dim = d->dim;
   const int64_t per_layer = d->B * inner * cap;
   const float scale = 1.0f / sqrtf((float)d->dim_head);
@@ -498,7 +530,7 @@ extern "C" int tribe_encoder_extend_fwd(const tribe_encoder_desc* d, float* x, v
   for (int l = 0; l < d->depth; ++l) {
     const tribe_encoder_layer& L = d->layers_host[l];
     TRIBE_REQUIRE(L.attn_norm_g && L.w_qkv && L.w_out && L.ff_norm_g && L.w_ff1 && L.b_ff1 && L.w_ff2 && L.b_ff2,
-                  "tribe_encoder_extend_fwd: layer %d has a null parameter", l);
+                  "%s: layer %d has a null parameter", name, l);
     rc = tribe_scalenorm_fwd(x, M, dim, L.attn_norm_g, d->norm_gain_scale, d->norm_eps, p.xn, TRIBE_BF16, stream);
     if (rc) return rc;
     tribe_gemm_desc g = Linear(TRIBE_ROLE_QKV, M, p.xn, dim, L.w_qkv, nullptr, p.qkv, 3 * inner, TRIBE_BF16);
@@ -506,10 +538,17 @@ extern "C" int tribe_encoder_extend_fwd(const tribe_encoder_desc* d, float* x, v
     rc = tribe_gemm_bf16(&g, stream);
     if (rc) return rc;
     uint16_t *kc = k_cache + l * per_layer, *vc = v_cache + l * per_layer;
-    rc = tribe_kv_append_block(p.qkv, d->B, d->T, d->heads, d->dim_head, d->rot_dim, d->rotary_interleaved, d->cos_tab, d->sin_tab, pos, kc, vc,
-                               cap, stream);
-    if (rc) return rc;
-    rc = tribe_attention_extend_fwd(p.qkv, 3 * inner, kc, vc, d->B, d->heads, d->dim_head, cap, pos, d->T, scale, p.ao, stream);
+    if (pos_slots) {
+      rc = tribe_kv_append_slots(p.qkv, d->B, d->T, d->heads, d->dim_head, d->rot_dim, d->rotary_interleaved, d->cos_tab, d->sin_tab, pos_slots,
+                                 kc, vc, cap, stream);
+      if (rc) return rc;
+      rc = tribe_attention_extend_slots_fwd(p.qkv, 3 * inner, kc, vc, d->B, d->heads, d->dim_head, cap, pos_slots, d->T, scale, p.ao, stream);
+    } else {
+      rc = tribe_kv_append_block(p.qkv, d->B, d->T, d->heads, d->dim_head, d->rot_dim, d->rotary_interleaved, d->cos_tab, d->sin_tab, pos, kc,
+                                 vc, cap, stream);
+      if (rc) return rc;
+      rc = tribe_attention_extend_fwd(p.qkv, 3 * inner, kc, vc, d->B, d->heads, d->dim_head, cap, pos, d->T, scale, p.ao, stream);
+    }
     if (rc) return rc;
     g = Linear(TRIBE_ROLE_OUT_PROJ, M, p.ao, inner, L.w_out, nullptr, x, dim, TRIBE_F32).residual(x);
     g.res_scale = L.attn_res_scale;
@@ -529,6 +568,28 @@ extern "C" int tribe_encoder_extend_fwd(const tribe_encoder_desc* d, float* x, v
     if (rc) return rc;
   }
   return tribe_scalenorm_fwd(x, M, dim, d->final_norm_g, d->norm_gain_scale, d->norm_eps, y, y_dtype, stream);
+}
+}  // namespace
+
+extern "C" int tribe_encoder_extend_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache,
+                                        uint16_t* v_cache, int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream) {
+  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_extend_fwd: null descriptor");
+  TRIBE_REQUIRE(d->T >= 1 && cap > 0 && pos >= 0 && pos + d->T <= cap,
+                "tribe_encoder_extend_fwd: k=%lld positions from pos=%lld outside the cache capacity %lld (k >= 1, pos >= 0, pos + k <= cap)",
+                (long long)d->T, (long long)pos, (long long)cap);
+  return extend_body("tribe_encoder_extend_fwd", d, x, y, y_dtype, k_cache, v_cache, cap, pos, nullptr, workspace, workspace_bytes, stream);
+}
+
+// every sequence at a position of its own: pos int32 [B] on the device (-1 = takes no part)
+extern "C" int tribe_encoder_extend_slots_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache,
+                                              uint16_t* v_cache, int64_t cap, const int32_t* pos, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  TRIBE_REQUIRE(d != nullptr, "tribe_encoder_extend_slots_fwd: null descriptor");
+  TRIBE_REQUIRE(d->T >= 1 && cap > 0 && d->T <= cap,
+                "tribe_encoder_extend_slots_fwd: k=%lld positions per sequence do not fit the cache capacity %lld (1 <= k <= cap)",
+                (long long)d->T, (long long)cap);
+  TRIBE_REQUIRE(pos != nullptr, "tribe_encoder_extend_slots_fwd: null pointer");
+  return extend_body("tribe_encoder_extend_slots_fwd", d, x, y, y_dtype, k_cache, v_cache, cap, 0, pos, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tribe_voxel_head_fwd(const uint16_t* x, int64_t B, int64_t T, int64_t C_pad, const uint16_t* w_packed, int64_t S,

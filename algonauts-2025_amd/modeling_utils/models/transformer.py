@@ -33,6 +33,11 @@ layer, csrc/attn_decode.hip), and `prefill(x[B, T0, dim], cache)` is the causal 
 cache (tribe_encoder_prefill_fwd).  `extend(x[B, k, dim], cache)` appends a block of k positions to a cache that holds any number of them
 (tribe_encoder_extend_fwd: k rows per sequence through every GEMM, tribe_kv_append_block, and the rectangular causal flash kernel
 tribe_attention_extend_fwd, csrc/attention.hip, against the cache plus the block itself).  Inference only, like `forward`.
+
+Independent timelines share one cache through slots: `new_slots(batch_size, max_len)` makes an `EncoderSlots` (the same k / v tensors plus one
+position per sequence), and `step_slots(x[B, dim], slots, active)` / `extend_slots(x[B, k, dim], slots, active)` advance any subset of the
+slots, each from its own position (tribe_encoder_step_slots_fwd / tribe_encoder_extend_slots_fwd: the launches of `step` / `extend` with
+the cache write and the attention in their position-per-sequence forms); `slots.reset([b])` frees a finished slot for the next timeline.
 """
 
 from __future__ import annotations
@@ -121,6 +126,65 @@ class EncoderCache:
     def reset(self) -> None:
         """Forget every position: the next step is position 0 again.  (The slots are not cleared: nothing at or beyond `pos` is read.)"""
         self.pos = 0
+
+
+class EncoderSlots:
+    """The keys and values of independent timelines streamed through one causal encoder (HipEncoder.new_slots): `k`, `v` as in EncoderCache,
+    bf16 [depth, B, heads, max_len, dim_head], and `positions`, the number of positions each of the B slots holds.  A call of
+    `step_slots` / `extend_slots` advances any subset of the slots; a finished slot is reset and refilled while the others carry on."""
+
+    def __init__(self, depth: int, batch_size: int, heads: int, max_len: int, dim_head: int, device: torch.device | str | None):
+        shape = (depth, batch_size, heads, max_len, dim_head)
+        self.k = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        self.v = torch.zeros(shape, dtype=torch.bfloat16, device=device)
+        self.positions: list[int] = [0] * batch_size
+
+    @property
+    def batch_size(self) -> int:
+        return self.k.shape[1]
+
+    @property
+    def max_len(self) -> int:
+        return self.k.shape[3]
+
+    @property
+    def device(self) -> torch.device:
+        return self.k.device
+
+    def reset(self, slots: tp.Sequence[int] | None = None) -> None:
+        """Forget every position of the given slots (None: of all): their next step is position 0 again.  (Nothing is cleared: no cache slot
+        at or beyond a position is read.)"""
+        B = self.batch_size
+        if slots is None:
+            self.positions = [0] * B
+            return
+        for b in slots:
+            if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < B:
+                raise ValueError(f"EncoderSlots.reset: slot index {b!r} outside [0, {B})")
+        for b in slots:
+            self.positions[b] = 0
+
+    def select(self, what: str, active: tp.Sequence[int] | tp.Sequence[bool] | None) -> list[bool]:
+        """`active` -- None (all slots), slot indices, or a bool sequence of length B -- as one flag per slot."""
+        B = self.batch_size
+        if active is None:
+            return [True] * B
+        if isinstance(active, torch.Tensor):
+            active = active.tolist()
+        active = list(active)
+        if active and all(isinstance(a, bool) for a in active):
+            if len(active) != B:
+                raise ValueError(f"{what}: the active mask holds {len(active)} flags for {B} slots")
+            flags = active
+        else:
+            flags = [False] * B
+            for b in active:
+                if isinstance(b, bool) or not isinstance(b, int) or not 0 <= b < B:
+                    raise ValueError(f"{what}: active slot index {b!r} outside [0, {B})")
+                flags[b] = True
+        if not any(flags):
+            raise ValueError(f"{what}: active is empty: a call advances at least one slot")
+        return flags
 
 
 class HipEncoder(nn.Module):
@@ -303,6 +367,99 @@ class HipEncoder(nn.Module):
             raise ValueError("HipEncoder.extend: k must be at least 1")
         x2d = x.detach().to(torch.float32).reshape(B * k, D).clone()
         return self.extend_tokens(x2d, B, k, cache, torch.float32).view(B, k, D)
+
+    # -- slots: independent timelines in one cache, a position per sequence ------------------
+    def new_slots(self, batch_size: int, max_len: int, device: torch.device | str | None = None) -> EncoderSlots:
+        """`batch_size` empty slots of up to `max_len` positions each, on `device` (default: where the parameters are)."""
+        self._require_causal("new_slots")
+        if batch_size < 1 or max_len < 1:
+            raise ValueError(f"HipEncoder.new_slots: batch_size={batch_size} and max_len={max_len} must be positive")
+        if device is None:
+            device = next(self.parameters()).device
+        return EncoderSlots(self.depth, batch_size, self.heads, max_len, self.dim_head, device)
+
+    def _check_slots(self, what: str, x: torch.Tensor, slots: EncoderSlots, steps: int, active) -> list[bool]:
+        """Validates a slot call before anything is launched; returns one flag per slot."""
+        self._require_causal(what)
+        if not isinstance(slots, EncoderSlots):
+            raise TypeError(f"HipEncoder.{what}: slots must be an EncoderSlots (HipEncoder.new_slots), got {type(slots)}")
+        want = (self.depth, slots.batch_size, self.heads, slots.max_len, self.dim_head)
+        if tuple(slots.k.shape) != want:
+            raise ValueError(f"HipEncoder.{what}: the slots {tuple(slots.k.shape)} were not made for this encoder ({want})")
+        if x.shape[0] != slots.batch_size:
+            raise ValueError(f"HipEncoder.{what}: batch size {x.shape[0]} does not match the {slots.batch_size} slots")
+        if x.shape[-1] != self.dim:
+            raise ValueError(f"HipEncoder.{what}: expected last dim {self.dim}, got {x.shape[-1]}")
+        if x.device != slots.device:
+            raise ValueError(f"HipEncoder.{what}: x is on {x.device}, the slots on {slots.device}")
+        return self._select_slots(f"HipEncoder.{what}", slots, steps, active)
+
+    @staticmethod
+    def _select_slots(what: str, slots: EncoderSlots, steps: int, active, filled: str = "positions filled") -> list[bool]:
+        """One flag per slot for `active`, after checking that every active slot has room for `steps` more positions (the one place this
+        is checked: HipEncoder.step_slots / extend_slots and SlotStream.push / push_block all come through here)."""
+        if steps < 1:
+            raise ValueError(f"{what}: k must be at least 1")
+        flags = slots.select(what, active)
+        for b, on in enumerate(flags):
+            if on and slots.positions[b] + steps > slots.max_len:
+                raise ValueError(f"{what}: slot {b}: {slots.positions[b]} {filled} + {steps} would run past max_len={slots.max_len}")
+        return flags
+
+    @staticmethod
+    def _slot_mask(flags: list[bool], device: torch.device) -> torch.Tensor | None:
+        """bool [B, 1] on the device (None: every slot is active), copied without waiting for the device."""
+        if all(flags):
+            return None
+        return torch.tensor(flags, dtype=torch.bool).pin_memory().to(device, non_blocking=True).view(-1, 1)
+
+    def step_slots_tokens(self, x2d: torch.Tensor, slots: EncoderSlots, flags: list[bool],
+                          out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+        """x2d f32 [B, dim], CONSUMED (finite rows for inactive slots) -> y [B, dim]: active slot b at slots.positions[b], which advances.
+        The rows of inactive slots are not meaningful."""
+        pos = [p if on else -1 for p, on in zip(slots.positions, flags)]
+        y = ops.encoder_step_slots(x2d, self.packed(), slots.k, slots.v, pos, out_dtype)
+        slots.positions = [p + 1 if on else p for p, on in zip(slots.positions, flags)]
+        return y
+
+    def extend_slots_tokens(self, x2d: torch.Tensor, B: int, k: int, slots: EncoderSlots, flags: list[bool],
+                            out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+        """x2d f32 [B*k, dim] (row b*k + t), CONSUMED -> y [B*k, dim]: active slot b at positions slots.positions[b] .. +k-1; it advances by k."""
+        pos = [p if on else -1 for p, on in zip(slots.positions, flags)]
+        y = ops.encoder_extend_slots(x2d, self.packed(), slots.k, slots.v, pos, k, out_dtype)
+        slots.positions = [p + k if on else p for p, on in zip(slots.positions, flags)]
+        return y
+
+    def step_slots(self, x: torch.Tensor, slots: EncoderSlots, active: tp.Sequence[int] | tp.Sequence[bool] | None = None) -> torch.Tensor:
+        """x [B, dim] -> y [B, dim]: `step` for independent timelines.  Active slot b (`active`: None = all, slot indices, or a bool sequence
+        of length B) is computed at its own position slots.positions[b], which then advances by 1; the rows of inactive slots come back as
+        zeros, and their positions and cache runs are untouched.  One call costs what one `step` at this batch size costs
+        (tribe_encoder_step_slots_fwd), and does not synchronise the device with the host.  Inference only, like `step`: eval semantics,
+        none of attn_dropout, ff_dropout, layer_dropout."""
+        if x.ndim != 2:
+            raise ValueError(f"HipEncoder.step_slots: expected [B, dim], got {tuple(x.shape)}")
+        flags = self._check_slots("step_slots", x, slots, 1, active)
+        mask = self._slot_mask(flags, x.device)
+        x2d = x.detach().to(torch.float32).clone().contiguous()
+        if mask is not None:
+            x2d = torch.where(mask, x2d, 0.0)
+        y = self.step_slots_tokens(x2d, slots, flags, torch.float32)
+        return y if mask is None else torch.where(mask, y, 0.0)
+
+    def extend_slots(self, x: torch.Tensor, slots: EncoderSlots, active: tp.Sequence[int] | tp.Sequence[bool] | None = None) -> torch.Tensor:
+        """x [B, k, dim] -> y [B, k, dim]: `extend` for independent timelines -- the next k positions of every active slot, each from its own
+        position (tribe_encoder_extend_slots_fwd); k is the same for all slots of a call.  Inactive slots as in `step_slots`.
+        Inference only, like `step`."""
+        if x.ndim != 3:
+            raise ValueError(f"HipEncoder.extend_slots: expected [B, k, dim], got {tuple(x.shape)}")
+        B, k, D = x.shape
+        flags = self._check_slots("extend_slots", x, slots, k, active)
+        mask = self._slot_mask(flags, x.device)
+        x3 = x.detach().to(torch.float32).clone()
+        if mask is not None:
+            x3 = torch.where(mask.view(B, 1, 1), x3, 0.0)
+        y = self.extend_slots_tokens(x3.reshape(B * k, D).contiguous(), B, k, slots, flags, torch.float32).view(B, k, D)
+        return y if mask is None else torch.where(mask.view(B, 1, 1), y, 0.0)
 
 
 class TransformerEncoderConfig(pydantic.BaseModel):

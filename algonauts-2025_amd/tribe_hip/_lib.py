@@ -297,6 +297,11 @@ SIGNATURES = {
     "tribe_attention_extend_fwd": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, i64, i64, i64, f32, vp, vp]),
     "tribe_encoder_extend_workspace_bytes": (sz, [C.POINTER(EncoderDesc), i64]),
     "tribe_encoder_extend_fwd": (C.c_int, [C.POINTER(EncoderDesc), vp, vp, i32, vp, vp, i64, i64, vp, sz, vp]),
+    "tribe_kv_append_slots": (C.c_int, [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+    "tribe_attention_decode_slots_fwd": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, i64, vp, i64, f32, vp, vp, sz, vp]),
+    "tribe_attention_extend_slots_fwd": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, i64, vp, i64, f32, vp, vp]),
+    "tribe_encoder_step_slots_fwd": (C.c_int, [C.POINTER(EncoderDesc), vp, vp, i32, vp, vp, i64, vp, i64, vp, sz, vp]),
+    "tribe_encoder_extend_slots_fwd": (C.c_int, [C.POINTER(EncoderDesc), vp, vp, i32, vp, vp, i64, vp, vp, sz, vp]),
     "tribe_voxel_head_fwd": (C.c_int, [vp, i64, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp]),
     "tribe_adaptive_avg_pool_fwd": (C.c_int, [vp, i64, i64, vp, i64, vp]),
     "tribe_mse_fwd": (C.c_int, [vp, vp, i64, vp, vp, sz, vp]),

@@ -974,6 +974,139 @@ def encoder_extend(x: torch.Tensor, pack: EncoderPack, k_cache: torch.Tensor, v_
     return y
 
 
+# ---- slots: every sequence of a cache at a position of its own ----
+def _slot_positions(what: str, pos: tp.Sequence[int], B: int, k: int, cap: int) -> list[int]:
+    """The host copy of a call's positions, checked before any launch: one int per sequence, -1 (takes no part) or 0 .. cap - k."""
+    if isinstance(pos, torch.Tensor) or not isinstance(pos, (list, tuple)):
+        raise TypeError(f"{what}: pos must be a list or tuple of ints (the wrapper builds the device array), got {type(pos)}")
+    if len(pos) != B:
+        raise ValueError(f"{what}: pos holds {len(pos)} positions for B={B} sequences")
+    if k < 1:
+        raise ValueError(f"{what}: k={k} must be at least 1")
+    out = []
+    for b, p in enumerate(pos):
+        if isinstance(p, bool) or not isinstance(p, int):
+            raise TypeError(f"{what}: pos[{b}] must be an int, got {type(p)}")
+        if p != -1 and not 0 <= p <= cap - k:
+            raise ValueError(f"{what}: pos[{b}]={p} .. +k={p + k} outside the cache capacity {cap} (-1 marks a sequence that takes no part)")
+        out.append(p)
+    return out
+
+
+def _slot_array(pos: list[int], device: torch.device) -> torch.Tensor:
+    """int32 [B] on the device.  Staged through pinned memory and copied on the current stream: the host does not wait for the device."""
+    return torch.tensor(pos, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+
+
+def _slot_tables(what: str, rot_dim: int, cos: torch.Tensor | None, sin: torch.Tensor | None, cap: int, device: torch.device) -> None:
+    if rot_dim:
+        for name, t in (("cos", cos), ("sin", sin)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 2 or t.shape[1] != rot_dim // 2 or t.shape[0] < cap \
+                    or not t.is_contiguous() or t.device != device:
+                raise ValueError(f"{what}: {name} must be a contiguous f32 [>= cap={cap}, rot_dim/2={rot_dim // 2}] table on {device}")
+
+
+def kv_append_slots(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: tp.Sequence[int], k: int, rot_dim: int,
+                    cos: torch.Tensor | None, sin: torch.Tensor | None, interleaved: bool) -> torch.Tensor:
+    """tribe_kv_append_slots: kv_append_block with a position per sequence.  Row b*k + t of the fused bf16 qkv [B*k, 3*heads*dim_head] is
+    rotated in place at position pos[b] + t and stored into slot pos[b] + t of sequence b (cos / sin f32 [>= cap, rot_dim/2]); pos[b] == -1:
+    neither the rows nor the cache run of sequence b are touched.  Returns qkv."""
+    what = "tribe_kv_append_slots"
+    B, heads, cap, dim_head = _kv_caches(what, k_cache, v_cache, 4)
+    pos = _slot_positions(what, pos, B, k, cap)
+    _block_rows(what, qkv, "qkv", torch.bfloat16, B, k, 3 * heads * dim_head, True, k_cache.device)
+    _slot_tables(what, rot_dim, cos, sin, cap, k_cache.device)
+    _cuda(qkv, torch.bfloat16, "qkv")
+    dpos = _slot_array(pos, qkv.device)
+    check(lib().tribe_kv_append_slots(qkv.data_ptr(), B, k, heads, dim_head, rot_dim, int(interleaved), _p(cos) if rot_dim else None,
+                                      _p(sin) if rot_dim else None, dpos.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), cap, _stream()),
+          what)
+    return qkv
+
+
+def attention_decode_slots(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: tp.Sequence[int], n_max: int,
+                           scale: float) -> torch.Tensor:
+    """tribe_attention_decode_slots_fwd: attention_decode with n_b = pos[b] + 1 keys for sequence b (pos[b] == -1: takes no part, its row
+    comes back as zeros); n_max bounds every n_b and fixes the key split (attention_decode_splits(B, heads, n_max)) -> bf16 [B, heads*dim_head]."""
+    what = "tribe_attention_decode_slots_fwd"
+    B, heads, cap, dim_head = _kv_caches(what, k_cache, v_cache, 4)
+    if dim_head not in DECODE_DIM_HEADS:
+        raise ValueError(f"{what}: dim_head={dim_head} must be one of {DECODE_DIM_HEADS}")
+    _step_rows(what, q, "q", torch.bfloat16, B, heads * dim_head, k_cache.device)
+    pos = _slot_positions(what, pos, B, 1, cap)
+    if not 1 <= n_max <= cap:
+        raise ValueError(f"{what}: n_max={n_max} keys outside 1 .. capacity {cap}")
+    if max(pos) + 1 > n_max:
+        raise ValueError(f"{what}: n_max={n_max} is no upper bound of the key counts pos[b] + 1 (largest: {max(pos) + 1})")
+    _cuda(q, torch.bfloat16, "q", contiguous=False)
+    dpos = _slot_array(pos, q.device)
+    out = torch.empty(B, heads * dim_head, dtype=torch.bfloat16, device=q.device)
+    nbytes = lib().tribe_attention_decode_workspace_bytes(B, heads, dim_head, n_max)
+    ws = workspace(nbytes, q.device, tag="decode")
+    check(lib().tribe_attention_decode_slots_fwd(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), B, heads, dim_head, cap,
+                                                 dpos.data_ptr(), n_max, scale, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), what)
+    return out
+
+
+def attention_extend_slots(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: tp.Sequence[int], k: int,
+                           scale: float) -> torch.Tensor:
+    """tribe_attention_extend_slots_fwd: attention_extend with the k query rows of sequence b at positions pos[b] .. pos[b]+k-1 against its
+    first pos[b]+k slots (kv_append_slots first); pos[b] == -1: takes no part, its rows come back as zeros -> bf16 [B*k, heads*dim_head]."""
+    what = "tribe_attention_extend_slots_fwd"
+    B, heads, cap, dim_head = _kv_caches(what, k_cache, v_cache, 4)
+    if dim_head not in DECODE_DIM_HEADS:
+        raise ValueError(f"{what}: dim_head={dim_head} must be one of {DECODE_DIM_HEADS}")
+    pos = _slot_positions(what, pos, B, k, cap)
+    _block_rows(what, q, "q", torch.bfloat16, B, k, heads * dim_head, False, k_cache.device)
+    _cuda(q, torch.bfloat16, "q", contiguous=False)
+    dpos = _slot_array(pos, q.device)
+    out = torch.empty(B * k, heads * dim_head, dtype=torch.bfloat16, device=q.device)
+    check(lib().tribe_attention_extend_slots_fwd(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), B, heads, dim_head, cap,
+                                                 dpos.data_ptr(), k, scale, out.data_ptr(), _stream()), what)
+    return out
+
+
+def encoder_step_slots(x: torch.Tensor, pack: EncoderPack, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: tp.Sequence[int],
+                       out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """tribe_encoder_step_slots_fwd: encoder_step with sequence b at position pos[b] (-1: takes no part; its row still runs through the norms
+    and GEMMs -- pass finite values -- and its output row is to be discarded).  x f32 [B, dim] is consumed; returns final-normed y [B, dim].
+    No host-device synchronisation: the positions travel as a pinned int32 array on the current stream."""
+    what = "tribe_encoder_step_slots_fwd"
+    B, cap = _encoder_caches(what, pack, x, k_cache, v_cache)
+    _step_rows(what, x, "x", torch.float32, B, pack.dim, k_cache.device)
+    if x.shape[1] != pack.dim or not x.is_contiguous():
+        raise ValueError(f"{what}: x must be contiguous [B={B}, dim={pack.dim}], got shape {tuple(x.shape)}")
+    pos = _slot_positions(what, pos, B, 1, cap)
+    _cuda(x, torch.float32, "x")
+    dpos = _slot_array(pos, x.device)
+    d = _encoder_desc(pack, B, 1, *pack.tables(cap, x.device))
+    y = torch.empty(B, pack.dim, dtype=out_dtype, device=x.device)
+    nbytes = lib().tribe_encoder_step_workspace_bytes(C.byref(d), cap)
+    ws = workspace(nbytes, x.device)
+    check(lib().tribe_encoder_step_slots_fwd(C.byref(d), x.data_ptr(), y.data_ptr(), _DT[out_dtype], k_cache.data_ptr(), v_cache.data_ptr(), cap,
+                                             dpos.data_ptr(), max(max(pos) + 1, 1), ws.data_ptr(), ws.numel(), _stream()), what)
+    return y
+
+
+def encoder_extend_slots(x: torch.Tensor, pack: EncoderPack, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: tp.Sequence[int], k: int,
+                         out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """tribe_encoder_extend_slots_fwd: encoder_extend with the k rows of sequence b at positions pos[b] .. pos[b]+k-1 (-1: takes no part, as in
+    encoder_step_slots).  x f32 [B*k, dim] (row b*k + t) is consumed; returns final-normed y [B*k, dim]."""
+    what = "tribe_encoder_extend_slots_fwd"
+    B, cap = _encoder_caches(what, pack, x, k_cache, v_cache)
+    pos = _slot_positions(what, pos, B, k, cap)
+    _block_rows(what, x, "x", torch.float32, B, k, pack.dim, True, k_cache.device)
+    _cuda(x, torch.float32, "x")
+    dpos = _slot_array(pos, x.device)
+    d = _encoder_desc(pack, B, k, *pack.tables(cap, x.device))
+    y = torch.empty(B * k, pack.dim, dtype=out_dtype, device=x.device)
+    nbytes = lib().tribe_encoder_extend_workspace_bytes(C.byref(d), cap)
+    ws = workspace(nbytes, x.device)
+    check(lib().tribe_encoder_extend_slots_fwd(C.byref(d), x.data_ptr(), y.data_ptr(), _DT[out_dtype], k_cache.data_ptr(), v_cache.data_ptr(),
+                                               cap, dpos.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), what)
+    return y
+
+
 # --------------------------------------------------------------------------------------
 # voxel head, pool, losses
 # --------------------------------------------------------------------------------------

@@ -368,6 +368,45 @@ size_t tribe_encoder_extend_workspace_bytes(const tribe_encoder_desc* d, int64_t
 int tribe_encoder_extend_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
                              int64_t cap, int64_t pos, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- slots: every sequence of a cache at a position of its own (independent timelines in one cache) ----
+ * pos: a device array int32 [B], 4-byte aligned.  pos[b] is the number of positions sequence ("slot") b already holds; -1 marks a slot that
+ * takes no part in the call.  A kernel cannot report a bad value without a synchronisation, so none ever dereferences a position outside
+ * [0, cap - k]: a sequence with such a value is treated exactly as one that takes no part.  Callers validate their host copy.
+ *
+ * tribe_kv_append_slots: tribe_kv_append_block with a position per sequence.  Row b * k + t of the fused bf16 qkv [B * k, 3 * heads *
+ *   dim_head] is rotated in place at position pos[b] + t and its k and v heads are stored into slot pos[b] + t of sequence b -- the block
+ *   append's arithmetic, bit for bit; k = 1 is the step.  Neither the cache run nor the qkv rows of a sequence that takes no part are
+ *   touched.  cos / sin f32 [>= cap, rot_dim / 2].  1 <= k <= cap.  One launch.
+ * tribe_attention_decode_slots_fwd: tribe_attention_decode_fwd with n_b = pos[b] + 1 keys for sequence b.  n_max (host, 1 <= n_max <= cap)
+ *   is an upper bound of every n_b; the kernel clamps n_b to it.  tribe_attention_decode_splits(B, heads, n_max) workgroups per (b, h), the
+ *   chunk tribe_attention_decode_fwd takes at n = n_max: split s of sequence b owns keys [s * chunk, min(n_b, (s + 1) * chunk)), which may
+ *   be empty, and the parts are merged in split order by the same rule -- no atomics, the same call gives the same bits, and with every
+ *   pos[b] + 1 == n_max the bits are those of tribe_attention_decode_fwd(..., n = n_max).  The out row of a sequence that takes no part is
+ *   written as zeros (bf16 +0).  Nothing at or beyond slot n_b of sequence b is read.  Workspace:
+ *   tribe_attention_decode_workspace_bytes(B, heads, dim_head, n_max).
+ * tribe_attention_extend_slots_fwd: tribe_attention_extend_fwd with the k query rows of sequence b at positions pos[b] .. pos[b] + k - 1
+ *   against its slots 0 .. pos[b] + k - 1 (tribe_kv_append_slots first).  Every workgroup reads the position of its own sequence: the
+ *   bits of sequence b are those of tribe_attention_extend_fwd run on that sequence alone at pos = pos[b].  The rows of a sequence that
+ *   takes no part are written as zeros; nothing at or beyond slot pos[b] + k is read.
+ * tribe_encoder_step_slots_fwd / tribe_encoder_extend_slots_fwd: tribe_encoder_step_fwd / tribe_encoder_extend_fwd with the two
+ *   cache-aware launches of every layer in their slot forms and the same workspace (tribe_encoder_step_workspace_bytes /
+ *   tribe_encoder_extend_workspace_bytes, which size by cap).  The step takes n_max as above.  Rows of sequences that take no part run
+ *   through the norms and GEMMs like any other row and their outputs are to be discarded (their attention rows are zeros): pass finite
+ *   values, zeros for example; rows are not compacted.  d->cos_tab / sin_tab hold at least cap rows. */
+int tribe_kv_append_slots(uint16_t* qkv, int64_t B, int64_t k, int32_t heads, int32_t dim_head, int32_t rot_dim, int32_t interleaved,
+                          const float* cos_tab, const float* sin_tab, const int32_t* pos, uint16_t* k_cache, uint16_t* v_cache, int64_t cap,
+                          void* stream);
+int tribe_attention_decode_slots_fwd(const uint16_t* q, int64_t ld_q, const uint16_t* k_cache, const uint16_t* v_cache, int64_t B,
+                                     int32_t heads, int32_t dim_head, int64_t cap, const int32_t* pos, int64_t n_max, float scale,
+                                     uint16_t* out, void* workspace, size_t workspace_bytes, void* stream);
+int tribe_attention_extend_slots_fwd(const uint16_t* q, int64_t ld_q, const uint16_t* k_cache, const uint16_t* v_cache, int64_t B,
+                                     int32_t heads, int32_t dim_head, int64_t cap, const int32_t* pos, int64_t k, float scale, uint16_t* out,
+                                     void* stream);
+int tribe_encoder_step_slots_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+                                 int64_t cap, const int32_t* pos, int64_t n_max, void* workspace, size_t workspace_bytes, void* stream);
+int tribe_encoder_extend_slots_fwd(const tribe_encoder_desc* d, float* x, void* y, int32_t y_dtype, uint16_t* k_cache, uint16_t* v_cache,
+                                   int64_t cap, const int32_t* pos, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * a16-a18: building blocks of the frozen extractors (HF transformers architectures)
  * ------------------------------------------------------------------------- */
