@@ -39,6 +39,11 @@ Contents
                    VoxelHead, the losses), their case and branch tables, the
                    bit-exact and per-element bounded criteria, and emulated faults.
 
+* `optim_ref`   -- float64 statements of the Adam / AdamW step (plain and clipped) and
+                   of the SWA running average with derived per-element bounds, an
+                   overflow rule for non-finite gradients, the case set, and an f32
+                   restatement with injectable faults.
+
 Pinning status (see DESIGN.md "Oracle")
 ---------------------------------------
 * Everything that lives in the reference's own files (SubjectLayers,

@@ -8,7 +8,9 @@ Bounds (derived, none fitted):
                coefficient of 1 leaves the bits alone
   clamp        exact
   fused step   bit for bit the in-place scale followed by the plain step; against torch.optim.Adam on the CPU the tolerances of
-               test_hip_adam_matches_torch_adam (rtol 2e-6, atol 2e-7): the coefficient's rounding is an order below them
+               test_hip_adam_matches_torch_adam (rtol 2e-6, atol 2e-7): the coefficient's rounding is an order below them; per
+               element against float64, with the coefficient and the limit given, under the derived bounds of oracle/optim_ref.py
+               in tests/test_gpu_optim_bounds.py::test_clipped
 """
 
 import functools
